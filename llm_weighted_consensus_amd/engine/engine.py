@@ -1066,6 +1066,9 @@ class LLMEngine:
         or weight-streaming shapes the planner's isolated timings rank the same way, and a serving engine
         meets many small buckets — each A/B captures ~20 graphs (measured: ~10 s of a 256-request load test)."""
         self.step_ab[bk.B] = {}
+        if bk.B in getattr(self.model, "pinned", {}):  # a fixed plan (LlamaModel.pin_step_plan): nothing to race
+            self.step_ab[bk.B] = {"choice": "pinned"}
+            return
         mode = os.environ.get("LWC_STEP_AB", "1")
         if mode == "0" or not hasattr(self.model, "step_plans"):
             return

@@ -146,6 +146,7 @@ class LlamaModel:
         self.final_norm_weight: Optional[torch.Tensor] = None  # the final norm's weight once lm_head holds it
         self.chain: Optional[ops.NormChain] = None
         self.chain_m: dict = {}  # decode batch M -> (use the chain, qkv tile width)
+        self.pinned: dict = {}  # decode batch M -> a fixed step plan (pin_step_plan): nothing is timed at M
         # ``fold_norms=False``: models that never decode through lm_head (the decoder-as-embedder) skip it
         if (fold_norms and self.device.type == "cuda" and not self.fp8_dense and type(self) is LlamaModel
                 and os.environ.get("LWC_NORM_FOLD", "1") != "0" and isinstance(self.layers[0], LayerWeights)):
@@ -401,6 +402,9 @@ class LlamaModel:
         mixed chunked-prefill steps (their M varies step to step); ``lm_head``: tune the vocabulary
         projection too (mixed steps only project the decode rows and completed prompts' last tokens);
         ``only``: the epilogues to tune (e.g. ("swiglu",): the gate|up projection alone)."""
+        if M in self.pinned and not bucket and only is None:
+            self._apply_pinned(M)
+            return
         if self.g8_ws is None or not isinstance(self.layers[0], LayerWeights) or self.fp8_dense:
             return
         cfg, L = self.cfg, self.layers[0]
@@ -421,6 +425,27 @@ class LlamaModel:
             gemm_plan.tune(x, self.lm_head, ws=self.g8_ws, bucket=bucket)
         if self.norm_folded and not bucket and lm_head:
             self._tune_chain(M, x, xa, xf)
+
+    def pin_step_plan(self, M: int, plan: dict) -> None:
+        """Fix the decode step's plan at batch M (the form of :meth:`step_plans`' entries: ``choices`` per
+        projection, ``chain`` for the folded norms): :meth:`tune_gemms` and the engine's in-step A/B then time
+        nothing at M, so every run of the process executes the same kernels and computes the same values
+        (timed choices flip between near-equal candidates from run to run)."""
+        self.pinned[M] = {"choices": dict(plan["choices"]), "chain": dict(plan["chain"]) if plan.get("chain") else None}
+
+    def _apply_pinned(self, M: int) -> None:
+        plan = self.pinned[M]
+        if self.g8_ws is None or not isinstance(self.layers[0], LayerWeights) or self.fp8_dense:
+            raise RuntimeError(f"a decode plan is pinned at batch {M}, but this model runs no planned GEMMs")
+        ch = plan["chain"]
+        if ch is not None and (ch["attn"] or ch["mlp"] or ch["final"]):
+            if not self.norm_folded:
+                raise RuntimeError(f"the plan pinned at batch {M} folds norms, but the model's norms are not folded")
+            if self.chain is None:  # as in _tune_chain: once, for every decode bucket
+                self.chain = ops.NormChain(max(M, 8192), self.cfg.hidden, self.cfg.rms_eps, self.device)
+            if M > self.chain.max_rows:
+                raise RuntimeError(f"the plan pinned at batch {M} exceeds the norm chain's {self.chain.max_rows} rows")
+        self.apply_step_plan(M, plan)
 
     def _tune_chain(self, M: int, x, xa, xf) -> None:
         """Decode batch M: decide, per norm point, between the norm kernel + the best projection backend and the

@@ -67,6 +67,16 @@ def choice(M: int, N: int, K: int, epi: str) -> str:
     return "blas"
 
 
+def pin(N: int, K: int, epi: str, c: str, M: Optional[int] = None) -> None:
+    """Fix the backend of the (N, K, epilogue) projection: at row count M, or (None) at every token bucket of the
+    encoder projections (:func:`linear_bias`: "bias" / "bias_gelu", :func:`linear_residual_`: "enc_residual").
+    A pinned shape is never timed, so every run of the process executes the same kernel for it."""
+    if c not in BACKENDS:
+        raise ValueError(f"unknown GEMM backend {c!r}")
+    for m in ([M] if M is not None else [1 << i for i in range(1, 17)]):
+        _CHOICE[(m, N, K, epi)] = c
+
+
 def _g8_ok(N: int, K: int, epi: str) -> bool:
     return K % 64 == 0 and N % (64 if epi == "swiglu" else 8) == 0
 

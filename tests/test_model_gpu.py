@@ -347,6 +347,44 @@ def test_folded_norm_chain_matches_unfolded(tiny, gpu, qkv_bn):
     assert _cos(got[B - 1], ref_logits[P]) > 0.995 and _cos(got[0], ref_logits[P]) > 0.995
 
 
+def test_pinned_step_plan_runs_untimed_and_repeats(gpu, monkeypatch):
+    """LlamaModel.pin_step_plan: at the pinned batch neither tune_gemms nor the engine's in-step A/B times
+    anything, the decode step runs exactly the pinned kernels (here the whole folded norm chain), and two fresh
+    models + engines sample the same tokens from the same seeds."""
+    from llm_weighted_consensus_amd.engine.engine import LLMEngine
+    from llm_weighted_consensus_amd.engine.sampling import SamplingParams
+    from llm_weighted_consensus_amd.engine.tokenizer import ByteTokenizer
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.llama import LlamaModel
+    from llm_weighted_consensus_amd.ops import gemm_plan
+
+    monkeypatch.setenv("LWC_STEP_AB_MIN", "1")  # without the pin, the A/B would race this small bucket
+    B = 256  # 2 prompts x 100 candidates decode in the 256-row bucket (one 256-row tile, 56 rows of it empty)
+    plan = {"choices": {n: "blas" for n in ("qkv", "o", "gu", "down", "lm")},
+            "chain": {"attn": True, "mlp": True, "final": True, "qkv_bn": 192, "qkv_var": 32, "gu_var": 64,
+                      "lm_var": 32, "lm_split": False, "o": "own32", "down": "sumsq"}}
+    saved, timed = dict(gemm_plan._CHOICE), set(gemm_plan.TIMINGS)
+    outs = []
+    try:
+        for _ in range(2):
+            m = LlamaModel(decoder_config("llama-tiny"), device=gpu, seed=0, max_position=1024)
+            m.pin_step_plan(B, plan)
+            tok = ByteTokenizer(m.cfg.vocab_size)
+            eng = LLMEngine(m, tok, num_blocks=2048, max_batch=B, max_model_len=256)
+            sp = SamplingParams(temperature=0.8, top_p=0.95, max_tokens=12, ignore_eos=True, seed=7)
+            outs.append(eng.generate([tok.encode("a prompt of some length " * 3), tok.encode("another one")], sp, n=100))
+            assert eng.step_ab[B] == {"choice": "pinned"}
+            assert not any(k[0] == B for k in set(gemm_plan.TIMINGS) - timed)  # nothing timed at the pinned batch
+            assert m.chain_m[B] == plan["chain"] and m.chain_ok(B)
+            assert m.plan_summary(B) == {"qkv": "g4 rs192 v32", "o": "g4 rs2 v32", "gu": "g4 rs v64",
+                                         "down": "blas+sumsq", "lm": "g4 rs v32"}
+    finally:
+        gemm_plan._CHOICE.clear()  # (module-wide, keyed by shape: later tests tune their own)
+        gemm_plan._CHOICE.update(saved)
+    assert outs[0] == outs[1]
+    assert len(outs[0]) == 2 and all(len(g) == 100 and all(len(c) == 12 for c in g) for g in outs[0])
+
+
 def test_folded_norms_keep_encode_and_logits_with_real_norm_weights(gpu):
     """Norm folding with NON-unit norm weights (random init has unit ones, which hide a dropped weight): the
     folded model's prefill logits and its encode() hidden states (the decoder-as-embedder output, which has
