@@ -30,6 +30,8 @@ int lwc_gemm4w(const void*, const void*, void*, const void*, int, int, int, int,
                float, int, int, int, int, float*, int*, hipStream_t);
 int lwc_rms_rowsumsq(const void*, float*, int, int, hipStream_t);
 int lwc_skinny_gemm(const void*, const void*, void*, const void*, int, int, int, int, int, int, hipStream_t);
+int lwc_lora_shrink(const void*, const void*, const int*, void*, int, int, int, int, int, hipStream_t);
+int lwc_lora_expand_add(void*, const void*, const void*, const int*, int, int, int, int, int, hipStream_t);
 int lwc_gemm8g_fp8(const void*, const void*, void*, const int*, const int*, const float*, const float*, int, int, int,
                    int, int, int, int, int, int, const void*, void*, int, hipStream_t);
 int lwc_moe_route(const void*, int, int, int, int*, float*, int*, int*, int*, hipStream_t);
@@ -481,6 +483,39 @@ void skinny_gemm(const at::Tensor& A, const at::Tensor& W, at::Tensor& C, const 
   CHECK_RC(lwc_skinny_gemm(A.data_ptr(), W.data_ptr(), C.data_ptr(), r, M, N, K, (int)A.stride(0), (int)C.stride(0),
                            (int)epi, cur_stream()),
            "skinny_gemm");
+}
+
+// batched LoRA (lora.hip): T[m] = X[m] . A[ids[m]]^T, then Y[m] += T[m] . B[ids[m]]^T; ids outside
+// [0, n_adapters) (-1) mean no adapter: the row of T is not written, the row of Y not touched
+void lora_check_ids(const at::Tensor& ids, int64_t M, const char* who) {
+  CHECK_GPU(ids); CHECK_DTYPE(ids, at::kInt); CHECK_CONTIG(ids);
+  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == M, who, ": ids must be int32 [M]");
+}
+
+void lora_shrink(const at::Tensor& X, const at::Tensor& A, const at::Tensor& ids, at::Tensor& T) {
+  CHECK_BF16(X); CHECK_BF16(A); CHECK_BF16(T); CHECK_CONTIG(A); CHECK_CONTIG(T);
+  TORCH_CHECK(X.dim() == 2 && A.dim() == 3 && T.dim() == 2 && X.stride(1) == 1, "lora_shrink: X [M, K] (rows may be strided), A [n, R, K], T [M, R]");
+  const int64_t M = X.size(0), K = X.size(1), R = A.size(1), n = A.size(0);
+  TORCH_CHECK(A.size(2) == K && T.size(0) == M && T.size(1) == R, "lora_shrink: shape mismatch");
+  TORCH_CHECK(M >= 1 && K % 64 == 0 && R % 16 == 0 && R >= 16 && R <= 192 && n >= 1 && n <= 64,
+              "lora_shrink: needs M >= 1, K % 64 == 0, R a multiple of 16 up to 192, at most 64 adapters");
+  lora_check_ids(ids, M, "lora_shrink");
+  CHECK_RC(lwc_lora_shrink(X.data_ptr(), A.data_ptr(), ids.data_ptr<int>(), T.data_ptr(), (int)M, (int)K, (int)R,
+                           (int)X.stride(0), (int)n, cur_stream()),
+           "lora_shrink");
+}
+
+void lora_expand_add(at::Tensor& Y, const at::Tensor& T, const at::Tensor& B, const at::Tensor& ids) {
+  CHECK_BF16(Y); CHECK_BF16(T); CHECK_BF16(B); CHECK_CONTIG(B); CHECK_CONTIG(T);
+  TORCH_CHECK(Y.dim() == 2 && B.dim() == 3 && T.dim() == 2 && Y.stride(1) == 1, "lora_expand_add: Y [M, N] (rows may be strided), T [M, R], B [n, N, R]");
+  const int64_t M = Y.size(0), N = Y.size(1), R = B.size(2), n = B.size(0);
+  TORCH_CHECK(B.size(1) == N && T.size(0) == M && T.size(1) == R, "lora_expand_add: shape mismatch");
+  TORCH_CHECK(M >= 1 && N % 8 == 0 && R % 16 == 0 && R >= 16 && R <= 192 && n >= 1 && n <= 64,
+              "lora_expand_add: needs M >= 1, N % 8 == 0, R a multiple of 16 up to 192, at most 64 adapters");
+  lora_check_ids(ids, M, "lora_expand_add");
+  CHECK_RC(lwc_lora_expand_add(Y.data_ptr(), T.data_ptr(), B.data_ptr(), ids.data_ptr<int>(), (int)M, (int)N, (int)R,
+                               (int)Y.stride(0), (int)n, cur_stream()),
+           "lora_expand_add");
 }
 
 // ss[r] = sum(x[r]^2): the single partial of the folded RMSNorm for the first projection of a chain
@@ -950,6 +985,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm8p", &gemm8p);
   m.def("gemm4w", &gemm4w);
   m.def("skinny_gemm", &skinny_gemm);
+  m.def("lora_shrink", &lora_shrink);
+  m.def("lora_expand_add", &lora_expand_add);
   m.def("rms_rowsumsq", &rms_rowsumsq);
   m.def("gemm8p_slots", &lwc_gemm8p_slots);
   m.def("moe_route", &moe_route);

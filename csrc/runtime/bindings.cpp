@@ -141,9 +141,11 @@ PYBIND11_MODULE(_runtime, m) {
       .def("free_sequence", &BlockManager::free_sequence)
       .def("set_prefix_caching", &BlockManager::set_prefix_caching)
       .def_property_readonly("prefix_caching", &BlockManager::prefix_caching)
-      .def("match_prefix", &BlockManager::match_prefix)
-      .def("add_sequence_cached", &BlockManager::add_sequence_cached)
-      .def("cache_prefix", &BlockManager::cache_prefix)
+      .def("match_prefix", &BlockManager::match_prefix, py::arg("tokens"), py::arg("salt") = (uint64_t)0)
+      .def("add_sequence_cached", &BlockManager::add_sequence_cached, py::arg("seq"), py::arg("tokens"),
+           py::arg("salt") = (uint64_t)0)
+      .def("cache_prefix", &BlockManager::cache_prefix, py::arg("seq"), py::arg("tokens"),
+           py::arg("salt") = (uint64_t)0)
       .def_property_readonly("num_cached_blocks", &BlockManager::num_cached_blocks)
       .def_property_readonly("num_evictable", &BlockManager::num_evictable)
       .def("length", &BlockManager::length)

@@ -72,6 +72,12 @@ static inline uint64_t mix64(uint64_t x) {
 
 static constexpr uint64_t kRootKey = 0x243f6a8885a308d3ULL;
 
+// First parent key of a chain: kRootKey itself for salt 0 (the keys of unsalted prompts), else a mix of the
+// two, so equal token blocks under different salts get different keys AND different parent keys.
+static inline uint64_t root_key(uint64_t salt) {
+  return salt == 0 ? kRootKey : mix64(kRootKey ^ mix64(salt ^ 0x9e3779b97f4a7c15ULL));
+}
+
 uint64_t BlockManager::chain_key(uint64_t parent, const int32_t* toks) const {
   uint64_t h = mix64(parent ^ 0x6a09e667f3bcc909ULL);
   for (int i = 0; i < block_size_; ++i) h = mix64(h ^ ((uint64_t)(uint32_t)toks[i] << 1 | 1ULL) ^ (uint64_t)i << 40);
@@ -95,10 +101,11 @@ void BlockManager::set_prefix_caching(bool on) {
   prefix_caching_ = on;
 }
 
-std::vector<int32_t> BlockManager::match_blocks(const std::vector<int32_t>& tokens, int64_t max_blocks) const {
+std::vector<int32_t> BlockManager::match_blocks(const std::vector<int32_t>& tokens, int64_t max_blocks,
+                                                uint64_t salt) const {
   std::vector<int32_t> out;
   if (!prefix_caching_) return out;
-  uint64_t parent = kRootKey;
+  uint64_t parent = root_key(salt);
   for (int64_t i = 0; i < max_blocks; ++i) {
     const int32_t* t = tokens.data() + i * block_size_;
     const uint64_t k = chain_key(parent, t);
@@ -114,15 +121,15 @@ std::vector<int32_t> BlockManager::match_blocks(const std::vector<int32_t>& toke
   return out;
 }
 
-int64_t BlockManager::match_prefix(const std::vector<int32_t>& tokens) const {
+int64_t BlockManager::match_prefix(const std::vector<int32_t>& tokens, uint64_t salt) const {
   if (tokens.empty()) return 0;
-  return (int64_t)match_blocks(tokens, ((int64_t)tokens.size() - 1) / block_size_).size() * block_size_;
+  return (int64_t)match_blocks(tokens, ((int64_t)tokens.size() - 1) / block_size_, salt).size() * block_size_;
 }
 
-int64_t BlockManager::add_sequence_cached(int64_t seq, const std::vector<int32_t>& tokens) {
+int64_t BlockManager::add_sequence_cached(int64_t seq, const std::vector<int32_t>& tokens, uint64_t salt) {
   if (seqs_.count(seq)) throw std::invalid_argument("BlockManager: sequence exists " + std::to_string(seq));
   const int64_t n = (int64_t)tokens.size();
-  const std::vector<int32_t> hit = match_blocks(tokens, n > 0 ? (n - 1) / block_size_ : 0);
+  const std::vector<int32_t> hit = match_blocks(tokens, n > 0 ? (n - 1) / block_size_ : 0, salt);
   const int need = blocks_for(n) - (int)hit.size();
   // the matched blocks may sit in the LRU list: taking them must not count them as allocatable
   int in_lru = 0;
@@ -140,11 +147,11 @@ int64_t BlockManager::add_sequence_cached(int64_t seq, const std::vector<int32_t
   return (int64_t)hit.size() * block_size_;
 }
 
-void BlockManager::cache_prefix(int64_t seq, const std::vector<int32_t>& tokens) {
+void BlockManager::cache_prefix(int64_t seq, const std::vector<int32_t>& tokens, uint64_t salt) {
   if (!prefix_caching_) return;
   const Seq& s = get(seq);
   const int64_t full = std::min<int64_t>((int64_t)tokens.size(), s.len) / block_size_;
-  uint64_t parent = kRootKey;
+  uint64_t parent = root_key(salt);
   for (int64_t i = 0; i < full && i < (int64_t)s.blocks.size(); ++i) {
     const int32_t b = s.blocks[i];
     const int32_t* t = tokens.data() + i * block_size_;

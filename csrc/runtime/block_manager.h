@@ -82,11 +82,13 @@ class BlockManager {
   bool prefix_caching() const { return prefix_caching_; }
   // Prompt tokens a new sequence would take from the cache: a multiple of BS, and at most
   // tokens.size() - 1 (the last prompt token is always computed: its logits start decoding).
-  int64_t match_prefix(const std::vector<int32_t>& tokens) const;
+  // `salt` (these three calls): prompts whose K/V depend on more than their tokens (a LoRA adapter) pass a
+  // non-zero salt; chains of different salts never share a block.  Salt 0 is the unsalted chain.
+  int64_t match_prefix(const std::vector<int32_t>& tokens, uint64_t salt = 0) const;
   // add_sequence(seq, tokens.size()) reusing the cached prefix blocks; returns the reused token count.
-  int64_t add_sequence_cached(int64_t seq, const std::vector<int32_t>& tokens);
+  int64_t add_sequence_cached(int64_t seq, const std::vector<int32_t>& tokens, uint64_t salt = 0);
   // Register the sequence's blocks that `tokens` (its prompt) fills completely.
-  void cache_prefix(int64_t seq, const std::vector<int32_t>& tokens);
+  void cache_prefix(int64_t seq, const std::vector<int32_t>& tokens, uint64_t salt = 0);
   int num_cached_blocks() const { return (int)by_key_.size(); }
   int num_evictable() const { return (int)lru_.size(); }
 
@@ -103,7 +105,7 @@ class BlockManager {
   void unregister(int32_t block);
   uint64_t chain_key(uint64_t parent, const int32_t* toks) const;
   // walk the cached chain of `tokens`; returns matched block ids (<= max_blocks of them)
-  std::vector<int32_t> match_blocks(const std::vector<int32_t>& tokens, int64_t max_blocks) const;
+  std::vector<int32_t> match_blocks(const std::vector<int32_t>& tokens, int64_t max_blocks, uint64_t salt = 0) const;
 
   int num_blocks_, block_size_;
   std::vector<int32_t> free_;

@@ -122,13 +122,23 @@ class LocalChatClient(ChatClient):
         self.first_chunk_timeout = first_chunk_timeout
         self.other_chunk_timeout = other_chunk_timeout
 
+    def _resolve(self, model: str):
+        """(service name, adapter or None) of a locally served model name: a service's own name, or
+        "<service>:<adapter>" for one of the LoRA adapters the service's model carries (``svc.adapters``)."""
+        if model in self.services:
+            return model, None
+        base, sep, adapter = model.rpartition(":")
+        if sep and base in self.services and adapter in getattr(self.services[base], "adapters", ()):
+            return base, adapter
+        return None
+
     def serves(self, model: str) -> bool:
-        return model in self.services
+        return self._resolve(model) is not None
 
     def _attempts(self, req: C.ChatCompletionCreateParams) -> List[str]:
         out: List[str] = []
         for m in [req.model] + list(req.models or []):
-            if m in self.services and m not in out:
+            if m not in out and self._resolve(m) is not None:
                 out.append(m)
         return out
 
@@ -183,7 +193,8 @@ class LocalChatClient(ChatClient):
         last_err: Optional[ChatError] = None
         for name in names:
             try:
-                stream, _group = self._start(self.services[name], name, request, ctx=ctx)
+                base, adapter = self._resolve(name)
+                stream, _group = self._start(self.services[base], name, request, ctx=ctx, adapter=adapter)
             except ChatError as e:
                 last_err = e
                 continue
@@ -216,9 +227,11 @@ class LocalChatClient(ChatClient):
             await stream.aclose()
 
     def _start(self, svc: EngineService, name: str, request: C.ChatCompletionCreateParams, embed: Optional[str] = None,
-               ctx: Any = None):
+               ctx: Any = None, adapter: Optional[str] = None):
         """Validate, render and submit one attempt; returns (its not yet started chunk generator, the
-        engine group).  ``embed``: the EngineGroup workers also embed the finished candidates."""
+        engine group).  ``embed``: the EngineGroup workers also embed the finished candidates.  ``adapter``:
+        the LoRA adapter of ``svc``'s model the attempt runs under (``name`` is then "<model>:<adapter>" and is
+        what the response's ``model`` echoes)."""
         tok = svc.engine.tokenizer
         template = getattr(svc, "chat_template", None) or template_for(svc.engine.cfg.name)
         prompt = render_chat_prompt(request.messages, request.tools, template)
@@ -230,6 +243,8 @@ class LocalChatClient(ChatClient):
             sp, tool_name = self.sampling_params(request, svc, len(ids))
         except ValueError as e:
             raise ChatError.invalid_request(str(e))
+        if adapter is not None:
+            sp = replace(sp, adapter=adapter)
         n = int(request.n or 1)
         if n < 1 or n > 128:
             raise ChatError.invalid_request(f"n must be between 1 and 128: {n}")
@@ -258,7 +273,7 @@ class LocalChatClient(ChatClient):
     # ---- candidates embedded where they were generated (EngineGroup workers)
     def _embedding_service_for(self, request: C.ChatCompletionCreateParams, embedding_model: str) -> Optional[str]:
         for name in self._attempts(request):
-            f = getattr(self.services[name], "embeds_in_workers", None)
+            f = getattr(self.services[self._resolve(name)[0]], "embeds_in_workers", None)
             if f is not None and f(embedding_model):
                 return name
         return None
@@ -280,7 +295,8 @@ class LocalChatClient(ChatClient):
             request = request.model_copy()
             request.messages = list(request.messages)
             replace_completion_messages(comps, request.messages)
-        stream, group = self._start(self.services[name], name, request, embed=embedding_model)
+        base, adapter = self._resolve(name)
+        stream, group = self._start(self.services[base], name, request, embed=embedding_model, adapter=adapter)
         agg = None
         async for chunk in self._timed_first(stream):
             if agg is None:

@@ -119,6 +119,8 @@ class SequenceGroup:
         self.timer = RequestTimer()
         self.prefilled: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self.pf_pos = -1  # chunked prefill: prompt tokens already in the KV cache (-1 = not started)
+        # index of params.adapter in the model's LoraSet (-1: the base model); adapter_id + 1 salts the prefix cache
+        self.adapter_id = -1
         # request context (context.RequestContext): admission priority, deadline, trace id
         self.priority = 0
         self.deadline: Optional[float] = None
@@ -130,13 +132,14 @@ class SequenceGroup:
 
 
 _F32_PARAMS = ("temperature", "top_p", "min_p", "top_a", "freq_pen", "pres_pen", "rep_pen")
-_I32_PARAMS = ("top_k", "count_rows", "bias_rows")
+_I32_PARAMS = ("top_k", "count_rows", "bias_rows", "lora_ids")
 
 
 class _GraphBucket:
     """Per batch-size bucket: the captured decode graph plus ONE int32 staging layout holding every
     per-step input (block tables, ctx lens, slots, positions, tokens, prefix tiles, sampler
-    parameters, Philox seeds/offsets).  The host side is two pinned buffers (alternating steps), the
+    parameters, each row's LoRA adapter index, Philox seeds/offsets).  The host side is two pinned buffers
+    (alternating steps), the
     device side one buffer whose views are the graph's inputs, so a step is one H2D copy."""
 
     def __init__(self, B: int, width: int, splits: int, max_tiles: int, device):
@@ -378,6 +381,8 @@ class LLMEngine:
         # report logprobs of grammar-constrained steps over the allowed tokens only (vote fast path:
         # at a constrained key letter that is the restricted softmax over the sibling letters)
         self.constrained_logprobs = constrained_logprobs
+        # LoRA adapters (models/lora.py): every forward then carries per-row adapter ids (-1 = none)
+        self.lora = getattr(model, "lora", None)
         self.buckets: Dict[int, _GraphBucket] = {}
         self.step_ab: Dict[int, dict] = {}  # bucket -> in-step A/B replay times per plan (_step_ab)
         self.inflight: Optional[_Step] = None
@@ -423,8 +428,16 @@ class LLMEngine:
         if len(prompt_ids) + params.max_tokens > self.max_model_len:
             raise ValueError(f"prompt ({len(prompt_ids)}) + max_tokens ({params.max_tokens}) exceeds "
                              f"max_model_len ({self.max_model_len})")
+        adapter_id = -1
+        if params.adapter is not None:
+            if self.lora is None:
+                raise ValueError(f"unknown adapter {params.adapter!r}: this model has no adapters")
+            adapter_id = self.lora.index(params.adapter)  # ValueError for an unknown name
+            if prefilled is not None:
+                raise ValueError("a prefilled prompt cannot run under an adapter (its K/V are the base model's)")
         g = SequenceGroup(self, list(prompt_ids), params, n, callback)
         g.prefilled = prefilled
+        g.adapter_id = adapter_id
         if isinstance(ctx, dict):
             g.priority = int(ctx.get("priority", 0) or 0)
             g.deadline = ctx.get("deadline")
@@ -527,14 +540,19 @@ class LLMEngine:
         return out
 
     # ------------------------------------------------------------------ prefill
-    def _run_prefill(self, prompts: List[List[int]], parents: List[int], use_cache: bool = False) -> torch.Tensor:
+    def _run_prefill(self, prompts: List[List[int]], parents: List[int], use_cache: bool = False,
+                     adapters: Optional[List[int]] = None) -> torch.Tensor:
         """Prefill packed prompts into freshly added transient sequences `parents`; returns the
         last-token logits [len(prompts), V].  With ``use_cache`` the prompts' cached prefix blocks are
         taken from the prefix cache and only the tails are computed (attention still sees the whole
-        prompt), and the prompts' full blocks are registered for later requests."""
+        prompt), and the prompts' full blocks are registered for later requests.  ``adapters``: each
+        prompt's LoRA adapter index (-1 / None: the base model); K and V depend on it, so it salts the
+        prompt's prefix-cache keys."""
         added: List[int] = []
+        if adapters is None:
+            adapters = [-1] * len(prompts)
         try:
-            return self._run_prefill_inner(prompts, parents, use_cache, added)
+            return self._run_prefill_inner(prompts, parents, use_cache, added, adapters)
         except BaseException:
             # a later prompt of the wave ran out of KV blocks (or the prefill failed): release the transient
             # parents already created and the cached blocks they acquired, then re-raise
@@ -542,12 +560,14 @@ class LLMEngine:
                 self.bm.free_sequence(pid)
             raise
 
-    def _run_prefill_inner(self, prompts, parents, use_cache, added) -> torch.Tensor:
+    def _run_prefill_inner(self, prompts, parents, use_cache, added, adapters) -> torch.Tensor:
         dev = self.device
         toks, pos, slots, cu, last, cached = [], [], [], [0], [], []
-        for pid, p in zip(parents, prompts):
+        row_ids: List[int] = []
+        for pid, p, aid in zip(parents, prompts, adapters):
             L = len(p)
-            c = int(self.bm.add_sequence_cached(pid, p)) if use_cache else 0
+            c = int(self.bm.add_sequence_cached(pid, p, aid + 1)) if use_cache else 0
+            row_ids.extend([aid] * (L - c))
             if not use_cache:
                 self.bm.add_sequence(pid, L)
             added.append(pid)
@@ -573,10 +593,11 @@ class LLMEngine:
         t_cu = _h2d(cu, torch.int32, dev)
         t_last = _h2d(last, torch.int64, dev)
         max_len = max(len(p) - c for p, c in zip(prompts, cached))
-        logits = self.model.prefill(t_tok, t_pos, t_slots, t_cu, max_len, t_last, self.cache, ctx=ctx)
+        kw = {"lora_ids": _h2d(row_ids, torch.int32, dev)} if self.lora is not None else {}
+        logits = self.model.prefill(t_tok, t_pos, t_slots, t_cu, max_len, t_last, self.cache, ctx=ctx, **kw)
         if use_cache:
-            for pid, p in zip(parents, prompts):
-                self.bm.cache_prefix(pid, p)
+            for pid, p, aid in zip(parents, prompts, adapters):
+                self.bm.cache_prefix(pid, p, aid + 1)
         self.stats["prefill_tokens"] += len(toks)
         return logits
 
@@ -614,7 +635,7 @@ class LLMEngine:
         logits_of: Dict[int, torch.Tensor] = {}
         for wave in self._prefill_waves(compute):
             lg = self._run_prefill([g.prompt_ids for g in wave], [-g.id for g in wave],
-                                   use_cache=self.prefix_caching)
+                                   use_cache=self.prefix_caching, adapters=[g.adapter_id for g in wave])
             for i, g in enumerate(wave):
                 logits_of[g.id] = lg[i]
         for g in imported:
@@ -709,6 +730,7 @@ class LLMEngine:
         toks: List[int] = []
         pos: List[int] = []
         slot_parts: List[np.ndarray] = []
+        row_ids: List[int] = []  # LoRA adapter index of every row (decode rows, then the chunks' token rows)
         dec_in = None
         if B:
             width = self.width
@@ -722,6 +744,7 @@ class LLMEngine:
             if src:  # input tokens still on the device (the previous step's sampler output)
                 from_prev = (_h2d([a for a, _ in src], torch.int64, dev), _h2d([b for _, b in src], torch.int64, dev))
             toks.extend(s.tokens[-1] if s.tokens else 0 for s in dec)
+            row_ids.extend(s.group.adapter_id for s in dec)
             pos.extend(ps.tolist())
             slot_parts.append(sl)
             dec_in = {"block_tables": _h2d(bt, torch.int32, dev), "ctx_lens": _h2d(cl, torch.int32, dev)}
@@ -737,6 +760,7 @@ class LLMEngine:
         for g, a, e in items:
             p = g.prompt_ids
             toks.extend(p[a:e])
+            row_ids.extend([g.adapter_id] * (e - a))
             pos.extend(range(a, e))
             slot_parts.append(slots_range(self.bm, -g.id, a, e - a))
             cu.append(cu[-1] + e - a)
@@ -757,9 +781,10 @@ class LLMEngine:
         t_tok = _h2d(toks, torch.int32, dev)
         if from_prev is not None:
             t_tok.index_copy_(0, from_prev[0], prev.tok_dev.index_select(0, from_prev[1]).to(torch.int32))
+        kw = {"lora_ids": _h2d(row_ids, torch.int32, dev)} if self.lora is not None else {}
         logits = self.model.forward_mixed(t_tok, _h2d(pos, torch.int32, dev),
                                           _h2d(np.concatenate(slot_parts), torch.int32, dev), self.cache, B, dec_in,
-                                          chunk_in, _h2d(rows, torch.int64, dev))
+                                          chunk_in, _h2d(rows, torch.int64, dev), **kw)
         if prev is not None:  # host bookkeeping of the previous step while this forward runs
             with span("decode.process"):
                 events += self._process(prev)
@@ -774,7 +799,8 @@ class LLMEngine:
         for i, (g, a, e) in enumerate(items):
             g.pf_pos = e
             if self.prefix_caching:  # register the blocks computed so far: prompts waiting on them can start
-                self.bm.cache_prefix(-g.id, g.prompt_ids if e == len(g.prompt_ids) else g.prompt_ids[:e])
+                self.bm.cache_prefix(-g.id, g.prompt_ids if e == len(g.prompt_ids) else g.prompt_ids[:e],
+                                     g.adapter_id + 1)
             if e == len(g.prompt_ids):
                 done.append((g, B + i))
         children: List[Sequence] = []
@@ -802,7 +828,7 @@ class LLMEngine:
         per prompt: equal chains = a shared prefix, block for block."""
         ch = g._chain
         if ch is None:
-            p, bs, h = g.prompt_ids, self.block_size, 0
+            p, bs, h = g.prompt_ids, self.block_size, g.adapter_id + 1  # (chains of different adapters differ)
             ch = []
             for i in range((len(p) - 1) // bs):
                 h = hash((h, tuple(p[i * bs:(i + 1) * bs])))
@@ -853,11 +879,11 @@ class LLMEngine:
             if g.pf_pos < 0:
                 if self.prefix_caching:
                     ch = self._block_chain(g)
-                    k = int(self.bm.match_prefix(p)) // bs
+                    k = int(self.bm.match_prefix(p, g.adapter_id + 1)) // bs
                     if k < len(ch) and ch[k] in pending:
                         deferred = True
                         continue
-                    g.pf_pos = int(self.bm.add_sequence_cached(-g.id, p))
+                    g.pf_pos = int(self.bm.add_sequence_cached(-g.id, p, g.adapter_id + 1))
                     self.stats["prefix_cache_tokens"] += g.pf_pos
                     pending.update(ch[g.pf_pos // bs:])
                 else:
@@ -892,7 +918,7 @@ class LLMEngine:
             if len(p) <= bs:
                 first.append(g)
                 continue
-            key = tuple(p[:bs])
+            key = (g.adapter_id,) + tuple(p[:bs])  # (heads are shared under one adapter only)
             lead = leaders.get(key)
             if lead is None:
                 leaders[key] = np.asarray(p, dtype=np.int64)
@@ -903,7 +929,7 @@ class LLMEngine:
             diff = np.nonzero(a[:n] != lead[:n])[0]
             common = int(diff[0]) if diff.size else n
             shared = min(common, len(p) - 1) // bs * bs
-            (second if shared > self.bm.match_prefix(p) else first).append(g)
+            (second if shared > self.bm.match_prefix(p, g.adapter_id + 1) else first).append(g)
         return [w for w in (first, second) if w]
 
     def _attach_rows(self, s: Sequence) -> None:
@@ -993,6 +1019,7 @@ class LLMEngine:
         st["rep_pen"] = col([p.repetition_penalty for p in ps], np.float32, 1.0)
         st["count_rows"] = col([s.count_row for s in seqs], np.int32, -1)
         st["bias_rows"] = col([s.group.bias_row for s in seqs], np.int32, -1)
+        st["lora_ids"] = col([s.group.adapter_id for s in seqs], np.int32, -1)  # padding rows: no adapter
         st["seeds"] = col([s.seed for s in seqs], np.int64)
         st["K"] = max((p.top_logprobs for p in ps), default=0)
         st["need_lp"] = any(p.logprobs for p in ps)
@@ -1021,10 +1048,12 @@ class LLMEngine:
         d = bk.d
         cascade = bool(bk.max_tiles) if cascade is None else cascade
 
+        kw = {"lora_ids": d["lora_ids"]} if self.lora is not None else {}
+
         def fwd():
             return self.model.decode(d["tokens"], d["positions"], d["slots"], d["block_tables"], d["ctx_lens"],
                                      self.cache, num_splits=bk.splits,
-                                     cascade_tiles=d["tiles"] if cascade else None)
+                                     cascade_tiles=d["tiles"] if cascade else None, **kw)
 
         if not self.use_graphs:
             bk.logits = fwd()

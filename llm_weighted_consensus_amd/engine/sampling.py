@@ -35,6 +35,9 @@ class SamplingParams:
     # constrained decoding (engine/constraints.py TokenConstraint): .start() / .advance(state, token) /
     # .is_done(state) / .mask_entry(state)
     constraint: Optional[object] = None
+    # LoRA adapter of the engine's model this request runs under (a name of its models.lora.LoraSet; None: the
+    # base model).  Resolved by LLMEngine.add_request; an unknown name is refused there
+    adapter: Optional[str] = None
 
     @property
     def uses_penalties(self) -> bool:

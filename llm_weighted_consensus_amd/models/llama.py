@@ -107,9 +107,20 @@ class _NullCache:
 class LlamaModel:
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
-                 fold_norms: bool = True):
+                 fold_norms: bool = True, lora=None):
         if cfg.num_experts and type(self) is LlamaModel:
             raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
+        # LoRA adapters (``lora``: a list of models/lora.py Adapters, laid out here once for this model's weights
+        # and device, or a LoraSet): rows of one batch carry different adapters (``lora_ids``).  The dense
+        # single-GPU bf16 decoder only, with unfolded norms: the adapters read the normalised rows
+        if lora is not None:
+            if type(self) is not LlamaModel or cfg.num_experts:
+                raise ValueError("LoRA adapters: only the dense single-GPU Llama decoder (no tensor parallelism, no MoE)")
+            if fp8_dense:
+                raise ValueError("LoRA adapters do not combine with fp8 weights")
+            if torch.device(device).type != "cuda":
+                raise ValueError("LoRA adapters run on the GPU kernels only")
+            fold_norms = False
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         self.cos, self.sin = rope_tables(cfg, self.device, max_position)
         if weights_path:
@@ -146,6 +157,15 @@ class LlamaModel:
         self.final_norm_weight: Optional[torch.Tensor] = None  # the final norm's weight once lm_head holds it
         self.chain: Optional[ops.NormChain] = None
         self.chain_m: dict = {}  # decode batch M -> (use the chain, qkv tile width)
+        self.lora = None
+        if lora is not None:
+            from .lora import LoraSet
+
+            gu_block = self.layers[0].gu_block
+            if not (isinstance(lora, LoraSet) and lora.laid_out_for(gu_block, self.device)):
+                lora = LoraSet(cfg, lora.adapters if isinstance(lora, LoraSet) else list(lora), gu_block, self.device,
+                               dtype)
+            self.lora = lora
         self.pinned: dict = {}  # decode batch M -> a fixed step plan (pin_step_plan): nothing is timed at M
         # ``fold_norms=False``: models that never decode through lm_head (the decoder-as-embedder) skip it
         if (fold_norms and self.device.type == "cuda" and not self.fp8_dense and type(self) is LlamaModel
@@ -286,14 +306,17 @@ class LlamaModel:
         return bool(c and (c["attn"] or c["mlp"] or c["final"])) and self.chain is not None and M <= self.chain.max_rows
 
     def _layers(self, x_res: torch.Tensor, cache: KVCache, positions, slots, attn_fn, rope_q: bool = True,
-                keep: Optional[torch.Tensor] = None, final_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                keep: Optional[torch.Tensor] = None, final_norm: Optional[torch.Tensor] = None,
+                lora_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Runs every layer; x_res is the residual stream (updated in place); returns the final
         normalised hidden state.  ``rope_q=False``: q leaves the qkv projection un-rotated and ``attn_fn``
         rotates it (the decode kernels' load-time RoPE).  ``keep`` (row indices): only those rows' final
         states are wanted (a prefill's last tokens, an embedder's pooled token) — the last layer still runs
         qkv / RoPE / the cache write / attention over every row (later tokens' keys and values), then its
         o projection, MLP and the final norm over the kept rows only; returns [len(keep), d].  ``final_norm``:
-        the weight of the last norm (default ``self.final_norm``; ones once it is folded into lm_head)."""
+        the weight of the last norm (default ``self.final_norm``; ones once it is folded into lm_head).
+        ``lora_ids`` (int32 per row, -1 = none; models built with ``lora=``): each row's adapter is added to
+        every projection it targets, after the base GEMM and in place (:meth:`_lora_add`)."""
         cfg = self.cfg
         T = x_res.shape[0]
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
@@ -309,8 +332,13 @@ class LlamaModel:
             h = ops.rmsnorm_quant_fp8(x_res, self.layers[0].attn_norm, cfg.rms_eps)
         else:
             h = ops.rmsnorm(x_res, self.layers[0].attn_norm, cfg.rms_eps)
+        lo = self.lora if lora_ids is not None else None
+        if lo is not None and not fused:
+            raise RuntimeError("LoRA adapters need the dense fused-residual layer path")
         for li, L in enumerate(self.layers):
             qkv = self._proj(h, L.wqkv)
+            if lo is not None:
+                self._lora_add(qkv, h, li, "qkv", lora_ids)
             ops.rope_kv_write(qkv, positions, self.cos, self.sin, cache.k[li], cache.v[li], Hq, Hkv, D, slots=slots,
                               rope_q=rope_q)
             attn = attn_fn(qkv, li)
@@ -319,9 +347,25 @@ class LlamaModel:
                     attn.reshape(T, Hq * D).index_select(0, keep)
                 x_res = x_res.index_select(0, keep)
                 T = x_res.shape[0]
+                if lo is not None:
+                    lora_ids = lora_ids.index_select(0, keep)
             nxt = (self.layers[li + 1].attn_norm if li + 1 < len(self.layers) else
                    self.final_norm if final_norm is None else final_norm)
-            if fused:
+            if fused and lo is not None:
+                a2 = attn.view(T, Hq * D)
+                gemm_plan.linear_add_(a2, L.wo, x_res, ws=self.g8_ws)
+                self._lora_add(x_res, a2, li, "o", lora_ids)
+                h = ops.rmsnorm(x_res, L.mlp_norm, cfg.rms_eps)
+                if lo.adapts_gate_up:  # the adapters add to the pre-activation: no fused SwiGLU epilogue
+                    gu = self._proj(h, L.w_gate_up)
+                    self._lora_add(gu, h, li, "gate_up", lora_ids)
+                    act = ops.silu_mul(gu, block=L.gu_block)
+                else:
+                    act = self._act(h, L)
+                gemm_plan.linear_add_(act, L.w_down, x_res, ws=self.g8_ws)
+                self._lora_add(x_res, act, li, "down", lora_ids)
+                h = ops.rmsnorm(x_res, nxt, cfg.rms_eps)
+            elif fused:
                 gemm_plan.linear_add_(attn.view(T, Hq * D), L.wo, x_res, ws=self.g8_ws)
                 h = ops.rmsnorm(x_res, L.mlp_norm, cfg.rms_eps)
                 gemm_plan.linear_add_(self._act(h, L), L.w_down, x_res, ws=self.g8_ws)
@@ -340,6 +384,14 @@ class LlamaModel:
                 down = self._mlp(h, L)
                 h = ops.rmsnorm(down, nxt, cfg.rms_eps, residual=x_res)
         return h
+
+    def _lora_add(self, y: torch.Tensor, x: torch.Tensor, li: int, proj: str, ids: torch.Tensor) -> None:
+        """y[m] += (x[m] . A[ids[m]]^T) . B[ids[m]]^T for layer ``li``'s projection ``proj`` (two launches,
+        csrc/kernels/lora.hip); nothing for a projection no adapter of the set targets."""
+        A = self.lora.A[li][proj]
+        if A is None:
+            return
+        ops.lora_expand_add_(y, ops.lora_shrink(x, A, ids), self.lora.B[li][proj], ids)
 
     # whether _mlp reads the bf16 rows of its (fp8-quantised) input too (the MoE router does)
     _mlp_reads_bf16 = False
@@ -670,7 +722,7 @@ class LlamaModel:
 
     def decode(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, block_tables: torch.Tensor,
                ctx_lens: torch.Tensor, cache: KVCache, num_splits: int = 1,
-               cascade_tiles: Optional[torch.Tensor] = None) -> torch.Tensor:
+               cascade_tiles: Optional[torch.Tensor] = None, lora_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One decode step for B sequences -> logits [B, V] bf16.  All inputs are device tensors
         (int32), so the whole call can be captured in a hipGraph.  Attention: ``cascade_tiles`` [T, 3] —
         the one-launch cascade kernel (shared prompt blocks read once per super-tile; the engine's
@@ -702,7 +754,7 @@ class LlamaModel:
 
         if self.chain_ok(B):
             return self._chain_layers(x, cache, positions, slots, attn_fn, not q_at_load, self.chain_m[B])
-        h = self._layers(x, cache, positions, slots, attn_fn, rope_q=not q_at_load)
+        h = self._layers(x, cache, positions, slots, attn_fn, rope_q=not q_at_load, lora_ids=lora_ids)
         return self._proj(h, self.lm_head)
 
     def encode(self, tokens: torch.Tensor, positions: torch.Tensor, cu_seqlens: torch.Tensor,
@@ -729,7 +781,8 @@ class LlamaModel:
                             final_norm=self.final_norm_weight)
 
     def prefill(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, cu_seqlens: torch.Tensor,
-                max_seqlen: int, last_idx: torch.Tensor, cache: KVCache, ctx: Optional[dict] = None) -> torch.Tensor:
+                max_seqlen: int, last_idx: torch.Tensor, cache: KVCache, ctx: Optional[dict] = None,
+                lora_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Prefill packed prompts (cu_seqlens) -> logits of each sequence's last token [nseq, V].
 
         ``ctx`` (cross-request prefix cache): the packed tokens are only each prompt's UNCACHED tail and
@@ -754,11 +807,13 @@ class LlamaModel:
                 return ops.prefill_attention_mx(q, k, v, cu_seqlens, max_seqlen, Hq, Hkv, self.scale, causal=True)
             return ops.prefill_attention(q, k, v, cu_seqlens, max_seqlen, Hq, Hkv, D, self.scale, causal=True)
 
-        h = self._layers(x, cache, positions, slots, attn_fn, keep=last_idx)  # last layer: o / MLP on these rows
+        # last layer: o / MLP on these rows
+        h = self._layers(x, cache, positions, slots, attn_fn, keep=last_idx, lora_ids=lora_ids)
         return F.linear(h, self.lm_head)
 
     def forward_mixed(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, cache: KVCache,
-                      n_dec: int, dec: Optional[dict], chunk: dict, logit_rows: torch.Tensor) -> torch.Tensor:
+                      n_dec: int, dec: Optional[dict], chunk: dict, logit_rows: torch.Tensor,
+                      lora_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ONE forward over [n_dec decode rows || prompt-chunk rows] (mixed chunked prefill): every projection
         is one GEMM over both; per layer the decode rows go to the paged decode kernel (``dec``: block_tables,
         ctx_lens and either cascade ``tiles`` or ``splits``) and the chunk rows to the paged-KV prefill kernel
@@ -789,5 +844,5 @@ class LlamaModel:
                                         lens=chunk.get("lens") if li == 0 else None)
             return out
 
-        h = self._layers(x, cache, positions, slots, attn_fn)
+        h = self._layers(x, cache, positions, slots, attn_fn, lora_ids=lora_ids)
         return self._proj(h.index_select(0, logit_rows), self.lm_head)

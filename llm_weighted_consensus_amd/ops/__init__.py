@@ -423,6 +423,26 @@ def skinny_gemm(A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tenso
     return out
 
 
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Batched LoRA down-projection (csrc/kernels/lora.hip): ``T[m] = x[m] . A[ids[m]]^T`` for ``x`` [M, K]
+    bf16 (rows may be strided), the stacked adapters ``A`` [n, R, K] and per-row int32 ``ids``; fp32
+    accumulation, ``T`` [M, R] bf16.  Rows whose id is -1 (no adapter) are NOT written: :func:`lora_expand_add_`
+    never reads them.  Needs K % 64 == 0, R a multiple of 16 up to 192, n <= 64."""
+    if out is None:
+        out = torch.empty(x.shape[0], A.shape[1], dtype=torch.bfloat16, device=x.device)
+    kernels().lora_shrink(x, A, ids, out)
+    return out
+
+
+def lora_expand_add_(y: torch.Tensor, t: torch.Tensor, B: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """Batched LoRA up-projection, in place (csrc/kernels/lora.hip): ``y[m] += t[m] . B[ids[m]]^T`` for ``y``
+    [M, N] bf16 (may be a column / row view of a wider buffer), ``t`` [M, R] from :func:`lora_shrink` and the
+    stacked ``B`` [n, N, R] (the adapter's alpha / r folded in).  Rows whose id is -1 stay bitwise unchanged.
+    Needs N % 8 == 0, 8-byte aligned rows of ``y``."""
+    kernels().lora_expand_add(y, t, B, ids)
+    return y
+
+
 def skinny_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
     return 0 < M <= 64 and K % 2048 == 0 and N % (64 if swiglu else 16) == 0
 

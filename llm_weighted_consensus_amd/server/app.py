@@ -264,7 +264,10 @@ def create_app(state: AppState) -> Starlette:
         return _json(m.to_obj())
 
     async def health(request: Request):
-        return JSONResponse({"status": "ok", "models": list(state.services), "embeddings": list(state.embedders)})
+        # every name a request's ``model`` may carry: the services and their LoRA adapters ("<model>:<adapter>")
+        models = [n for name, svc in state.services.items()
+                  for n in [name] + [f"{name}:{a}" for a in getattr(svc, "adapters", ())]]
+        return JSONResponse({"status": "ok", "models": models, "embeddings": list(state.embedders)})
 
     async def metrics(request: Request):
         return Response(state.metrics.render(state), media_type="text/plain; version=0.0.4")

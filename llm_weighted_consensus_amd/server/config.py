@@ -9,6 +9,13 @@ variables configure the local engine:
                     "tp": T (MoE decoders, BASELINE config 5) serves each replica tensor-parallel over T
                     consecutive LWC_GPUS entries — one process per GPU, the IPC one-shot all-reduce (C3)
                     inside every forward, the ranks stepping in lockstep behind the replica's rank 0
+                    "adapters": {"<adapter>": {"weights": "random:<seed>" | <PEFT directory>, "rank": 16,
+                    "alpha": 32, "targets": ["q", "k", "v", "o", "gate", "up", "down"], "std": 0.02}} serves LoRA
+                    adapters on this base model (models/lora.py): each is a voter of its own under the model
+                    name "<name>:<adapter>", all of them decoding in one batch on one copy of the weights.
+                    rank / alpha / targets / std describe a random adapter; a PEFT directory
+                    (adapter_config.json + adapter_model.safetensors) brings its own.  Dense Llama-family
+                    models only: refused with "tp" > 1, "fp8", MoE archs and in LWC_EMBED_MODELS
   LWC_EMBED_MODELS  JSON {name: {"arch": "bge-large-en-v1.5", "weights": "random:<seed>" | <path>}}
   LWC_GPU           device index for this process's engine (one process per GPU)
   LWC_GPUS          comma list of devices: serve each model through an EngineGroup (one worker process

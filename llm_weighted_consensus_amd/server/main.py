@@ -31,7 +31,12 @@ def build_state(cfg: Config, chat_client=None) -> AppState:
         from ..engine.service import EngineService
         from ..engine.tokenizer import load_tokenizer
         from ..models.config import decoder_config
+        from ..models.lora import check_model_spec
 
+        # LoRA adapters of the model specs; the combinations they do not run in are refused before any load
+        for name, spec in cfg.embed_models.items():
+            check_model_spec(name, spec, embedder=True)
+        adapters_of = {name: check_model_spec(name, spec) for name, spec in cfg.models.items()}
         if cfg.device == "cpu":
             if cfg.models:
                 raise ValueError("LWC_DEVICE=cpu serves embedding models only (decoders need an MI355X)")
@@ -42,6 +47,7 @@ def build_state(cfg: Config, chat_client=None) -> AppState:
         for name, spec in cfg.embed_models.items():
             embedders[name] = build_embedding_service(name, spec, dev)
         for name, spec in cfg.models.items():
+            adapters = adapters_of[name]  # LoRA adapters: each served as "<name>:<adapter>"
             dcfg = decoder_config(spec["arch"])
             mlen = int(spec.get("max_model_len", 4096))
             if cfg.gpus:  # one worker process per listed GPU behind one front end (LWC_GPUS=0: a single worker)
@@ -59,6 +65,7 @@ def build_state(cfg: Config, chat_client=None) -> AppState:
                                              respawn=cfg.respawn, max_respawns=cfg.max_respawns,
                                              respawn_backoff_s=cfg.respawn_backoff_s)
                 services[name].chat_template = spec.get("chat_template")
+                services[name].adapters = adapters
                 continue
             from ..engine.group import build_engine
 
@@ -70,6 +77,7 @@ def build_state(cfg: Config, chat_client=None) -> AppState:
                                     kv_reserve_tokens=cfg.kv_reserve_tokens), 0)
             services[name] = EngineService(eng, name)
             services[name].chat_template = spec.get("chat_template")
+            services[name].adapters = adapters
     remote = None
     bases = cfg.api_bases()
     if bases:

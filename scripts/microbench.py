@@ -723,6 +723,131 @@ def chain_ab(dev):
           f"{med['rmsnorm'] + med['lm blas']:.1f}, chain {med['lm g4 rs']:.1f}", flush=True)
 
 
+def lora_kernels(dev):
+    """Batched LoRA (lora.hip) on the Llama-3-8B projections at M = 4096 / 2048 rows and adapter ranks 16 / 64
+    (the fused q|k|v call runs 3 rank slots, gate|up 2): shrink and expand-add on a 4-adapter batch in
+    request-sized runs of 64 rows, and on a batch with no adapter at all (every id -1: what a configured but
+    unused adapter set costs per launch), next to the base projection from the same run, both as the model runs
+    it (the planner's backend, ops/gemm_plan.py, tuned here: qkv and the gate|up pre-activation plain, o and
+    down with the residual add in the GEMM) and through hipBLASLt alone (``F.linear``).  Bytes
+    each kernel must move: shrink reads X [M, K]; expand-add reads and writes Y [M, N].  Inputs rotate over
+    enough copies to exceed the 256 MB last-level cache; medians of 5 interleaved rounds."""
+    import torch.nn.functional as F
+
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.ops import gemm_plan
+
+    ws = ops.new_gemm8p_workspace(dev)
+    projs = [("qkv", 6144, 4096, 3), ("o", 4096, 4096, 1), ("gate_up", 28672, 4096, 2), ("down", 4096, 14336, 1)]
+    n_ad = 4
+    print("| proj | M | rank (R) | planner GEMM us | hipBLASLt us | shrink us | X MB | TB/s | expand us | Y r+w MB | TB/s | "
+          "shrink -1 us | expand -1 us |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for M in [int(m) for m in os.environ.get("LORA_M", "4096,2048").split(",")]:
+        ids = ((torch.arange(M, device=dev) // 64) % n_ad).to(torch.int32)
+        none = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        for name, N, K, slots in projs:
+            w = ((torch.rand(N, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16)
+            nx = max(2, min(8, -(-(512 << 20) // (M * K * 2))))
+            ny = max(2, min(8, -(-(512 << 20) // (M * N * 2))))
+            xs = [(torch.rand(M, K, device=dev) * 2 - 1).to(torch.bfloat16) for _ in range(nx)]
+            ys = [(torch.rand(M, N, device=dev) * 2 - 1).to(torch.bfloat16) for _ in range(ny)]
+            it = [0]
+
+            def nxt(pool):
+                it[0] += 1
+                return pool[it[0] % len(pool)]
+
+            res = name in ("o", "down")
+            choice = gemm_plan.tune(xs[0], w, "residual" if res else "plain", ws=ws)
+            if res:
+                def planner():
+                    return gemm_plan.linear_add_(nxt(xs), w, nxt(ys), ws=ws)
+            else:
+                def planner():
+                    return gemm_plan.linear(nxt(xs), w, ws=ws)
+
+            for rank in (16, 64):
+                R = rank * slots
+                A = ((torch.rand(n_ad, R, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16)
+                B = ((torch.rand(n_ad, N, R, device=dev) * 2 - 1) / R ** 0.5).to(torch.bfloat16)
+                T = torch.zeros(M, R, device=dev, dtype=torch.bfloat16)
+                runs = {"plan": planner, "base": lambda: F.linear(nxt(xs), w),
+                        "shrink": lambda: ops.lora_shrink(nxt(xs), A, ids, out=T),
+                        "expand": lambda: ops.lora_expand_add_(nxt(ys), T, B, ids),
+                        "shrink0": lambda: ops.lora_shrink(nxt(xs), A, none, out=T),
+                        "expand0": lambda: ops.lora_expand_add_(nxt(ys), T, B, none)}
+                t = {k: [] for k in runs}
+                for _ in range(5):
+                    for k, fn in runs.items():
+                        t[k].append(timeit(fn, iters=10, warm=2))
+                m = {k: sorted(v)[2] for k, v in t.items()}
+                xb, yb = M * K * 2, 2 * M * N * 2
+                print(f"| {name} | {M} | {rank} ({R}) | {m['plan']:.1f} ({choice}) | {m['base']:.1f} | {m['shrink']:.1f} | {xb / 1e6:.1f} | "
+                      f"{xb / m['shrink'] / 1e6:.2f} | {m['expand']:.1f} | {yb / 1e6:.1f} | {yb / m['expand'] / 1e6:.2f} | "
+                      f"{m['shrink0']:.1f} | {m['expand0']:.1f} |", flush=True)
+                del A, B, T
+            del w, xs, ys
+
+
+def lora_step(dev):
+    """One llama-3-8b decode step at B = 4096 (every sequence at position 32, captured in a graph, median of 20
+    replays) on three models built one after the other in this process: the plain model (norms folded, the
+    planner's chain), the plain model with unfolded norms, and a model with 4 rank-16 adapters on all seven
+    targets whose rows all carry id -1 — the price of having adapters configured but unused."""
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.llama import KVCache, LlamaModel
+    from llm_weighted_consensus_amd.models.lora import random_adapter
+
+    cfg = decoder_config("llama-3-8b")
+    B, pos = int(os.environ.get("LORA_STEP_B", "4096")), 32
+    i32 = dict(dtype=torch.int32, device=dev)
+    cache = KVCache(cfg, 3 * B, 16, dev)
+    bt = torch.arange(3 * B, **i32).view(B, 3)
+    tokens = torch.randint(0, cfg.vocab_size, (B,), device=dev).int()
+    positions = torch.full((B,), pos, **i32)
+    slots = (bt[:, 2] * 16).contiguous()
+    ctx = torch.full((B,), pos + 1, **i32)
+    none = torch.full((B,), -1, **i32)
+    res = {}
+    for label in ("plain", "plain unfolded norms", "adapters configured, all rows -1"):
+        kw = {}
+        if label.startswith("adapters"):
+            kw["lora"] = [random_adapter(f"a{i}", cfg, i, rank=16) for i in range(4)]
+        elif "unfolded" in label:
+            kw["fold_norms"] = False
+        model = LlamaModel(cfg, device=dev, seed=0, max_position=256, **kw)
+        model.tune_gemms(B)
+        dk = {"lora_ids": none} if model.lora is not None else {}
+
+        def fwd():
+            return model.decode(tokens, positions, slots, bt, ctx, cache, num_splits=1, **dk)
+
+        for _ in range(2):
+            fwd()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fwd()
+        ts = []
+        for _ in range(23):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            g.replay()
+            e.record()
+            e.synchronize()
+            ts.append(s.elapsed_time(e))
+        ts = sorted(ts[3:])
+        res[label] = ts[len(ts) // 2]
+        print(f"decode step B={B} [{label}]: median {res[label]:.3f} ms (min {ts[0]:.3f}, max {ts[-1]:.3f}) "
+              f"chain={model.chain_ok(B)} plan={model.plan_summary(B)}", flush=True)
+        del g, model
+        torch.cuda.empty_cache()
+    base = res["plain"]
+    for k, v in res.items():
+        print(f"  {k}: {v:.3f} ms  ({(v / base - 1) * 100:+.2f} % vs plain)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["gemm", "attn", "sample", "small"])
@@ -746,6 +871,10 @@ def main():
         serve_shapes(dev)
     if "skinny" in a.what:
         skinny_ab(dev)
+    if "lora" in a.what:
+        lora_kernels(dev)
+    if "lorastep" in a.what:
+        lora_step(dev)
     if "g48" in a.what:
         g48_ab(dev)
     if "g8ab" in a.what:
