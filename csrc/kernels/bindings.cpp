@@ -12,6 +12,8 @@ int lwc_rmsnorm_quant_fp8(const void*, void*, const void*, void*, int, int, floa
 int lwc_layernorm(const void*, const void*, const void*, const void*, const void*, void*, int, int, float, hipStream_t);
 int lwc_rope_kv_write(void*, const int*, const int*, const float*, const float*, void*, void*, int, int, int, int,
                       int, int, hipStream_t);
+int lwc_qknorm_rope_kv_write(void*, const int*, const int*, const float*, const float*, void*, void*, const void*,
+                             const void*, const void*, int, int, int, int, int, int, float, hipStream_t);
 int lwc_silu_mul(const void*, void*, int, int, int, hipStream_t);
 int lwc_embedding_gather(const void*, const int*, void*, int, int, int, hipStream_t);
 int lwc_kv_block_copy(void*, const int*, int, int, int, long long, hipStream_t);
@@ -186,6 +188,52 @@ void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const c10::opti
                              sin_t.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), T, (int)Hq, (int)Hkv,
                              (int)D, BS, rope_q ? 1 : 0, cur_stream()),
            "rope_kv_write");
+}
+
+// rope_kv_write with the Qwen attention-block steps in front of the rotation (csrc/kernels/qknorm.hip): the
+// q|k|v projection bias and the per-head RMSNorm of q and k, each optional.  head_dim 128 only.
+void qknorm_rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const c10::optional<at::Tensor>& slots,
+                          const at::Tensor& cos_t, const at::Tensor& sin_t, at::Tensor& k_cache, at::Tensor& v_cache,
+                          int64_t Hq, int64_t Hkv, int64_t D, bool rope_q, const c10::optional<at::Tensor>& bias,
+                          const c10::optional<at::Tensor>& q_weight, const c10::optional<at::Tensor>& k_weight,
+                          double eps) {
+  const char* who = "qknorm_rope_kv_write";
+  CHECK_BF16(qkv); CHECK_CONTIG(qkv);
+  CHECK_GPU(positions); CHECK_DTYPE(positions, at::kInt); CHECK_CONTIG(positions);
+  CHECK_GPU(cos_t); CHECK_GPU(sin_t); CHECK_CONTIG(cos_t); CHECK_CONTIG(sin_t);
+  CHECK_DTYPE(cos_t, at::kFloat); CHECK_DTYPE(sin_t, at::kFloat);
+  CHECK_BF16(k_cache); CHECK_BF16(v_cache); CHECK_CONTIG(k_cache);
+  TORCH_CHECK(D == 128, who, ": head_dim must be 128 (what the decode attention kernels take), got ", D);
+  TORCH_CHECK(Hq > 0 && Hkv > 0 && Hkv * D <= 4096, who, ": needs 1 <= Hkv <= 32 and Hq >= 1");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (Hq + 2 * Hkv) * D, who, ": qkv row is not (Hq+2Hkv)*D");
+  const int T = (int)qkv.size(0);
+  TORCH_CHECK(positions.numel() == T, who, ": positions length");
+  TORCH_CHECK(cos_t.dim() == 2 && sin_t.dim() == 2 && cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2 &&
+                  cos_t.size(0) == sin_t.size(0),
+              who, ": cos/sin table shape");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == D, who, ": k_cache shape");
+  check_v_cache(v_cache, k_cache, who);
+  const int BS = (int)k_cache.size(2);
+  const int* sp = nullptr;
+  if (slots.has_value() && slots->defined()) {
+    CHECK_GPU(*slots); CHECK_DTYPE(*slots, at::kInt); CHECK_CONTIG(*slots);
+    TORCH_CHECK(slots->numel() == T, who, ": slots length");
+    sp = slots->data_ptr<int>();
+  }
+  auto opt_bf16 = [&](const c10::optional<at::Tensor>& t, int64_t n, const char* name) -> const void* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(), who, ": ", name,
+                " must be a contiguous bf16 GPU tensor");
+    TORCH_CHECK(t->numel() == n, who, ": ", name, " has ", t->numel(), " elements, expected ", n);
+    return t->data_ptr();
+  };
+  const void* bp = opt_bf16(bias, (Hq + 2 * Hkv) * D, "bias");
+  const void* qp = opt_bf16(q_weight, D, "q_weight");
+  const void* kp = opt_bf16(k_weight, D, "k_weight");
+  CHECK_RC(lwc_qknorm_rope_kv_write(qkv.data_ptr(), positions.data_ptr<int>(), sp, cos_t.data_ptr<float>(),
+                                    sin_t.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), bp, qp, kp, T,
+                                    (int)Hq, (int)Hkv, (int)D, BS, rope_q ? 1 : 0, (float)eps, cur_stream()),
+           "qknorm_rope_kv_write");
 }
 
 // Optional q rotation inside the decode kernels: (cos [max_pos, D/2] fp32, sin, positions [B] int32) all
@@ -977,6 +1025,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_quant_fp8", &rmsnorm_quant_fp8);
   m.def("layernorm", &layernorm);
   m.def("rope_kv_write", &rope_kv_write);
+  m.def("qknorm_rope_kv_write", &qknorm_rope_kv_write);
   m.def("silu_mul", &silu_mul);
   m.def("embedding", &embedding);
   m.def("kv_block_copy", &kv_block_copy);

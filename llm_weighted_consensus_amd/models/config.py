@@ -29,8 +29,12 @@ class DecoderConfig:
     num_experts: int = 0
     experts_per_token: int = 0
     tie_embeddings: bool = False
-    bos_token_id: int = 1
+    bos_token_id: Optional[int] = 1  # None: the tokenizer prepends nothing (Qwen)
     eos_token_id: int = 2
+    # Qwen attention block: a bias on the q|k|v projections (Qwen2 / Qwen2.5); an RMSNorm over each q and k
+    # head's head_dim values, one weight shared by all heads, before the rotation (Qwen3)
+    qkv_bias: bool = False
+    qk_norm: bool = False
 
     @property
     def qkv_dim(self) -> int:
@@ -39,6 +43,7 @@ class DecoderConfig:
     def params(self) -> int:
         d, f = self.hidden, self.ffn
         attn = d * self.qkv_dim + self.heads * self.head_dim * d
+        attn += (self.qkv_dim if self.qkv_bias else 0) + (2 * self.head_dim if self.qk_norm else 0)
         mlp = 3 * d * f * max(1, self.num_experts) + (d * self.num_experts if self.num_experts else 0)
         emb = self.vocab_size * d * (1 if self.tie_embeddings else 2)
         return self.layers * (attn + mlp + 2 * d) + emb + d
@@ -79,6 +84,30 @@ DECODERS = {
     "mixtral-tiny": DecoderConfig("mixtral-tiny", 4096, 512, 2, 8, 2, 128, 512, rope_theta=1e6, max_position=2048,
                                   num_experts=4, experts_per_token=2),
 }
+
+
+def _qwen(name: str, vocab: int, hidden: int, layers: int, heads: int, kv_heads: int, ffn: int, tie: bool,
+          **flags) -> DecoderConfig:
+    return DecoderConfig(name, vocab, hidden, layers, heads, kv_heads, 128, ffn, rope_theta=1e6, rms_eps=1e-6,
+                         max_position=32768, tie_embeddings=tie, bos_token_id=None, eos_token_id=151645, **flags)
+
+
+# Qwen3 (per-head q/k RMSNorm) and Qwen2.5 (q|k|v bias): the sizes whose GQA group divides 16 and whose
+# head_dim is 128, which is what the decode attention kernels take.  Qwen2.5-7B/14B/32B and Qwen3-14B (groups
+# of 7 and 5) and the 0.5B / 1.5B models (head_dim 64 or a group of 6) are not registered.
+DECODERS.update({
+    "qwen3-0.6b": _qwen("qwen3-0.6b", 151936, 1024, 28, 16, 8, 3072, True, qk_norm=True),
+    "qwen3-4b": _qwen("qwen3-4b", 151936, 2560, 36, 32, 8, 9728, True, qk_norm=True),
+    "qwen3-8b": _qwen("qwen3-8b", 151936, 4096, 36, 32, 8, 12288, False, qk_norm=True),
+    "qwen3-32b": _qwen("qwen3-32b", 151936, 5120, 64, 64, 8, 25600, False, qk_norm=True),
+    "qwen2.5-3b": _qwen("qwen2.5-3b", 151936, 2048, 36, 16, 2, 11008, True, qkv_bias=True),
+    "qwen2.5-72b": _qwen("qwen2.5-72b", 152064, 8192, 80, 64, 8, 29568, False, qkv_bias=True),
+    # tests: the two attention-block variants at llama-tiny sizes
+    "qwen3-tiny": replace(_qwen("qwen3-tiny", 4096, 512, 2, 8, 2, 1024, True, qk_norm=True), max_position=2048,
+                          eos_token_id=2),
+    "qwen2-tiny": replace(_qwen("qwen2-tiny", 4096, 512, 2, 8, 2, 1024, False, qkv_bias=True), max_position=2048,
+                          eos_token_id=2),
+})
 
 ENCODERS = {
     "bge-small-en-v1.5": EncoderConfig("bge-small-en-v1.5", 30522, 384, 12, 12, 1536),

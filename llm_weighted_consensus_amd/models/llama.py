@@ -6,7 +6,8 @@ This is the local generation backend that replaces the reference's upstream prov
 Per layer (decode, B sequences):
     rmsnorm                       K1
     qkv  = x @ Wqkv^T             K6 (fused q|k|v weight)
-    rope + paged KV write         K2 (in place, one pass)
+    rope + paged KV write         K2 (in place, one pass; Qwen: K2q, the q|k|v bias and the per-head q / k
+                                      RMSNorm in the same pass, csrc/kernels/qknorm.hip)
     attn = paged GQA decode       K3 (cascade for forked candidates, else split-K)
     x   += attn @ Wo^T            K6 with the residual add in its epilogue, then K1
     act  = silu(x Wg^T) (x Wu^T)  K6 with SwiGLU in its epilogue (fused gate|up weight), or GEMM + K5
@@ -71,6 +72,10 @@ class LayerWeights:
     w_gate_up: torch.Tensor  # [2F, d]  rows: gate then up (gu_block 0) or interleaved in blocks of gu_block
     w_down: torch.Tensor    # [d, F]
     gu_block: int = 0
+    # Qwen attention block (cfg.qkv_bias / cfg.qk_norm), applied by ops.qknorm_rope_kv_write
+    bqkv: Optional[torch.Tensor] = None    # [(Hq+2Hkv)*D]  q|k|v projection bias
+    q_norm: Optional[torch.Tensor] = None  # [D]  per-head RMSNorm weight of q, shared by all heads
+    k_norm: Optional[torch.Tensor] = None  # [D]  the same for k
 
 
 class KVCache:
@@ -220,6 +225,15 @@ class LlamaModel:
                 w_gate_up=rnd(2 * F_, d),
                 w_down=rnd(d, F_, s=out_std),
             ))
+            # (drawn for flagged configs only, after the layer's matrices: every other arch draws the sequence
+            # it always drew)
+            if cfg.qkv_bias:
+                self.layers[-1].bqkv = rnd(qkv, s=0.05)
+            if cfg.qk_norm:
+                def norm_w():  # 1 + 0.3 N(0, 1), in fp32, then one cast
+                    return (1.0 + 0.3 * torch.randn(cfg.head_dim, generator=g, device=dev, dtype=torch.float32)).to(dt)
+
+                self.layers[-1].q_norm, self.layers[-1].k_norm = norm_w(), norm_w()
         self.final_norm = torch.ones(d, device=dev, dtype=dt)
         self.lm_head = self.embed if cfg.tie_embeddings else rnd(cfg.vocab_size, d)
 
@@ -237,11 +251,34 @@ class LlamaModel:
         def t(name):
             return sd[name].to(device=dev, dtype=dt).contiguous()
 
+        cfg = self.cfg
+        D = cfg.head_dim
+
+        def req(name, shape):
+            """A tensor a flagged config needs: absent, or of another shape than the config's, is an error
+            (a checkpoint of another architecture must not vote with part of its weights dropped)."""
+            if name not in sd:
+                raise ValueError(f"{path}: {cfg.name} needs {name}, which the checkpoint does not have")
+            if tuple(sd[name].shape) != tuple(shape):
+                raise ValueError(f"{path}: {name} has shape {tuple(sd[name].shape)}, {cfg.name} expects {tuple(shape)}")
+            return t(name)
+
+        def attn_extras(p):
+            out = {}
+            if cfg.qkv_bias:
+                out["bqkv"] = torch.cat([req(p + f"self_attn.{x}_proj.bias", (n * D,)) for x, n in
+                                         (("q", cfg.heads), ("k", cfg.kv_heads), ("v", cfg.kv_heads))]).contiguous()
+            if cfg.qk_norm:
+                out["q_norm"] = req(p + "self_attn.q_norm.weight", (D,))
+                out["k_norm"] = req(p + "self_attn.k_norm.weight", (D,))
+            return out
+
         self.embed = t("model.embed_tokens.weight")
         self.layers = []
         for i in range(self.cfg.layers):
             p = f"model.layers.{i}."
             self.layers.append(LayerWeights(
+                **attn_extras(p),
                 attn_norm=t(p + "input_layernorm.weight"),
                 wqkv=torch.cat([t(p + "self_attn.q_proj.weight"), t(p + "self_attn.k_proj.weight"),
                                 t(p + "self_attn.v_proj.weight")]).contiguous(),
@@ -285,8 +322,7 @@ class LlamaModel:
                 qkv = ops.gemm4w(x_res, L.wqkv, bn=plan["qkv_bn"], chain=ch, var=qv)
             else:
                 qkv = self._proj(ops.rmsnorm(x_res, ones, eps), L.wqkv)
-            ops.rope_kv_write(qkv, positions, self.cos, self.sin, cache.k[li], cache.v[li], Hq, Hkv, D, slots=slots,
-                              rope_q=rope_q)
+            self._rope_kv_write(qkv, L, positions, cache.k[li], cache.v[li], slots, rope_q)
             attn = attn_fn(qkv, li).reshape(T, Hq * D)
             self._residual_into(attn, L.wo, x_res, plan["o"] if plan["mlp"] else "plain")
             if plan["mlp"]:
@@ -339,8 +375,7 @@ class LlamaModel:
             qkv = self._proj(h, L.wqkv)
             if lo is not None:
                 self._lora_add(qkv, h, li, "qkv", lora_ids)
-            ops.rope_kv_write(qkv, positions, self.cos, self.sin, cache.k[li], cache.v[li], Hq, Hkv, D, slots=slots,
-                              rope_q=rope_q)
+            self._rope_kv_write(qkv, L, positions, cache.k[li], cache.v[li], slots, rope_q)
             attn = attn_fn(qkv, li)
             if keep is not None and li + 1 == len(self.layers):
                 attn = attn.index_select(keep) if isinstance(attn, ops.MXAct) else \
@@ -384,6 +419,21 @@ class LlamaModel:
                 down = self._mlp(h, L)
                 h = ops.rmsnorm(down, nxt, cfg.rms_eps, residual=x_res)
         return h
+
+    def _rope_kv_write(self, qkv: torch.Tensor, L, positions, k_cache, v_cache, slots, rope_q: bool) -> None:
+        """RoPE + the paged KV write of one layer, in place on ``qkv``: the Qwen kernel when the layer carries a
+        q|k|v bias or q/k norm weights (added / applied in the same pass, before the rotation), else
+        rope_kv_write.  q must leave here biased and normalised also on pure decode steps, where the attention
+        kernels rotate it as they load it."""
+        cfg = self.cfg
+        bias, qn, kn = getattr(L, "bqkv", None), getattr(L, "q_norm", None), getattr(L, "k_norm", None)
+        if bias is None and qn is None and kn is None:
+            ops.rope_kv_write(qkv, positions, self.cos, self.sin, k_cache, v_cache, cfg.heads, cfg.kv_heads,
+                              cfg.head_dim, slots=slots, rope_q=rope_q)
+        else:
+            ops.qknorm_rope_kv_write(qkv, positions, self.cos, self.sin, k_cache, v_cache, cfg.heads, cfg.kv_heads,
+                                     cfg.head_dim, slots=slots, rope_q=rope_q, bias=bias, q_weight=qn, k_weight=kn,
+                                     eps=cfg.rms_eps)
 
     def _lora_add(self, y: torch.Tensor, x: torch.Tensor, li: int, proj: str, ids: torch.Tensor) -> None:
         """y[m] += (x[m] . A[ids[m]]^T) . B[ids[m]]^T for layer ``li``'s projection ``proj`` (two launches,

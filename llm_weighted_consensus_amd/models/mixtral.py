@@ -66,6 +66,8 @@ class MixtralModel(LlamaModel):
                  ep_comm=None):
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
+        if cfg.qkv_bias or cfg.qk_norm:
+            raise NotImplementedError(f"{cfg.name}: the MoE decoder has no q|k|v bias and no q/k head norm")
         if ep_size > 1 and tp_size > 1:
             raise ValueError("choose TP or EP for the MoE decoder, not both")
         if cfg.num_experts % ep_size:

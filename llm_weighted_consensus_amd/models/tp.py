@@ -67,10 +67,17 @@ def shard_dense_layer(L: LayerWeights, cfg: DecoderConfig, rank: int, size: int)
     if L.gu_block:
         raise ValueError("shard before the gate|up interleave")
     gate, up = gu[rank * fl:(rank + 1) * fl], gu[F_ + rank * fl:F_ + (rank + 1) * fl]
+    # the q|k|v bias is cut like the rows of wqkv (this rank's heads); the q / k norm weights span one head's
+    # dims and are the same for every head: replicated
+    b = L.bqkv
+    if b is not None:
+        b = torch.cat([b[rank * hq * D:(rank + 1) * hq * D], b[Q + rank * hk * D:Q + (rank + 1) * hk * D],
+                       b[Q + K + rank * hk * D:Q + K + (rank + 1) * hk * D]]).contiguous()
     return LayerWeights(attn_norm=L.attn_norm, wqkv=torch.cat([q, k, v]).contiguous(),
                         wo=L.wo[:, rank * hq * D:(rank + 1) * hq * D].contiguous(), mlp_norm=L.mlp_norm,
                         w_gate_up=torch.cat([gate, up]).contiguous(),
-                        w_down=L.w_down[:, rank * fl:(rank + 1) * fl].contiguous())
+                        w_down=L.w_down[:, rank * fl:(rank + 1) * fl].contiguous(),
+                        bqkv=b, q_norm=L.q_norm, k_norm=L.k_norm)
 
 
 class TPLlamaModel(TensorParallel, LlamaModel):

@@ -127,6 +127,22 @@ def rope_kv_write(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor,
     kernels().rope_kv_write(qkv, positions, slots, cos, sin, k_cache, v_cache, int(Hq), int(Hkv), int(D), bool(rope_q))
 
 
+def qknorm_rope_kv_write(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                         k_cache: torch.Tensor, v_cache: torch.Tensor, Hq: int, Hkv: int, D: int,
+                         slots: Optional[torch.Tensor] = None, rope_q: bool = True,
+                         bias: Optional[torch.Tensor] = None, q_weight: Optional[torch.Tensor] = None,
+                         k_weight: Optional[torch.Tensor] = None, eps: float = 1e-6) -> None:
+    """:func:`rope_kv_write` for the Qwen attention block, in the same single pass (csrc/kernels/qknorm.hip):
+    ``bias`` [(Hq+2Hkv)*D] is added to q, k and v (Qwen2 / Qwen2.5), then ``q_weight`` / ``k_weight`` [D]
+    (shared by all heads) RMS-normalise every q / k head over its D values (Qwen3), then the rotation and the
+    cache write as in :func:`rope_kv_write`.  fp32 arithmetic, one rounding to bf16 at each store.  q goes
+    back to ``qkv`` biased and normalised always (rotated only with ``rope_q``); k and v go back where
+    :func:`rope_kv_write` writes k back (``rope_q`` or a padding row) and into the caches at ``slots``.
+    ``D`` must be 128."""
+    kernels().qknorm_rope_kv_write(qkv, positions, slots, cos, sin, k_cache, v_cache, int(Hq), int(Hkv), int(D),
+                                   bool(rope_q), bias, q_weight, k_weight, float(eps))
+
+
 def v_token(v_cache: torch.Tensor, block: int, t: int) -> torch.Tensor:
     """[Hkv, D] view of token `t` of block `block` in a 4-token-interleaved V cache."""
     return v_cache[block, :, t // 4, :, t % 4]

@@ -848,6 +848,103 @@ def lora_step(dev):
         print(f"  {k}: {v:.3f} ms  ({(v / base - 1) * 100:+.2f} % vs plain)")
 
 
+def qknorm(dev):
+    """qknorm_rope_kv_write (q|k|v bias, per-head q / k RMSNorm, RoPE, KV write) beside rope_kv_write at Llama-3-8B
+    head counts (32 / 8 / 128), T = 4096 and 64, both rope_q modes: interleaved rounds, median, and the bytes each
+    call has to move (from the shapes) over that time.  Then one decode layer at B = 4096 — (3-layer step - 1-layer
+    step) / 2 of graph replays, norms unfolded — for llama-3-8b, qwen3-8b and qwen3-8b's shapes without the q / k
+    norm (the same GEMMs on rope_kv_write)."""
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.llama import KVCache, LlamaModel, rope_tables
+
+    cfg = decoder_config("llama-3-8b")
+    Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+    cos, sin = rope_tables(cfg, dev, 4096)
+    bf = torch.bfloat16
+    bias = (0.05 * torch.randn(cfg.qkv_dim, device=dev)).to(bf)
+    qw, kw = [(1 + 0.3 * torch.randn(D, device=dev)).to(bf) for _ in range(2)]
+    feats = {"norms": dict(q_weight=qw, k_weight=kw), "bias": dict(bias=bias),
+             "both": dict(bias=bias, q_weight=qw, k_weight=kw)}
+
+    def nbytes(T, rope_q, q_work, v_back):
+        q, kv = T * Hq * D * 2, T * Hkv * D * 2
+        rd = kv + kv + (q if q_work else 0) + T * D * 4  # k, v, q; one cos + sin row per token
+        wr = kv + kv + (q if q_work else 0) + ((kv + (kv if v_back else 0)) if rope_q else 0)  # caches, q, k / v back
+        return rd + wr
+
+    for T in (4096, 64):
+        cache = KVCache(decoder_config("llama-3-8b", layers=1), T + 64, 16, dev)
+        qkv0 = torch.randn(T, cfg.qkv_dim, device=dev).to(bf)
+        qkv = qkv0.clone()
+        pos = torch.randint(0, 4000, (T,), device=dev, dtype=torch.int32)
+        slots = (torch.randperm(T, device=dev).to(torch.int32) * 16 + 5)
+        args = (qkv, pos, cos, sin, cache.k[0], cache.v[0], Hq, Hkv, D)
+        runs = {}
+        for rope_q in (True, False):
+            m = "q+k" if rope_q else "k only"
+            runs[f"rope_kv_write [{m}]"] = (lambda r=rope_q: ops.rope_kv_write(*args, slots=slots, rope_q=r),
+                                            nbytes(T, rope_q, rope_q, False))
+            for name, kwargs in feats.items():
+                runs[f"qknorm {name} [{m}]"] = (
+                    lambda r=rope_q, k=kwargs: ops.qknorm_rope_kv_write(*args, slots=slots, rope_q=r, eps=1e-6, **k),
+                    nbytes(T, rope_q, True, "bias" in kwargs))
+        ts = {k: [] for k in runs}
+        for _ in range(7):  # (in place on qkv: refreshed each round so the norms never see a drifted row)
+            for k, (fn, _) in runs.items():
+                qkv.copy_(qkv0)
+                ts[k].append(timeit(fn, iters=20, warm=3))
+        for k, (_, nb) in runs.items():
+            v = sorted(ts[k])
+            us = v[len(v) // 2]
+            print(f"T={T:5d} {k:32s}: {us:7.1f} us (min {v[0]:.1f}, max {v[-1]:.1f})  {nb / 1e6:7.1f} MB  "
+                  f"{nb / (us * 1e-6) / 1e12:5.2f} TB/s", flush=True)
+        del cache
+
+    B, pos = int(os.environ.get("QKNORM_STEP_B", "4096")), 32
+    i32 = dict(dtype=torch.int32, device=dev)
+    bt = torch.arange(3 * B, **i32).view(B, 3)
+    positions, ctx = torch.full((B,), pos, **i32), torch.full((B,), pos + 1, **i32)
+    slots = (bt[:, 2] * 16).contiguous()
+    res = {}
+    for label, arch, over in (("llama-3-8b", "llama-3-8b", {}), ("qwen3-8b", "qwen3-8b", {}),
+                              ("qwen3-8b shapes, no q/k norm", "qwen3-8b", {"qk_norm": False})):
+        step = {}
+        for nl in (1, 3):
+            c = decoder_config(arch, layers=nl, **over)
+            cache = KVCache(c, 3 * B, 16, dev)
+            model = LlamaModel(c, device=dev, seed=0, max_position=256, fold_norms=False)
+            model.tune_gemms(B)
+            tokens = torch.randint(0, c.vocab_size, (B,), device=dev).int()
+
+            def fwd():
+                return model.decode(tokens, positions, slots, bt, ctx, cache, num_splits=1)
+
+            for _ in range(2):
+                fwd()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fwd()
+            ts = []
+            for _ in range(23):
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                g.replay()
+                e.record()
+                e.synchronize()
+                ts.append(s.elapsed_time(e))
+            ts = sorted(ts[3:])
+            step[nl] = ts[len(ts) // 2]
+            print(f"decode step B={B} [{label}, {nl} layer(s)]: median {step[nl]:.3f} ms (min {ts[0]:.3f}, "
+                  f"max {ts[-1]:.3f}) plan={model.plan_summary(B)}", flush=True)
+            del g, model, cache
+            torch.cuda.empty_cache()
+        res[label] = (step[3] - step[1]) / 2
+    for k, v in res.items():
+        print(f"  one decode layer B={B} [{k}]: {v * 1e3:.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["gemm", "attn", "sample", "small"])
@@ -875,6 +972,8 @@ def main():
         lora_kernels(dev)
     if "lorastep" in a.what:
         lora_step(dev)
+    if "qknorm" in a.what:
+        qknorm(dev)
     if "g48" in a.what:
         g48_ab(dev)
     if "g8ab" in a.what:
