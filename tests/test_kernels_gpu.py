@@ -117,6 +117,13 @@ def test_rope_kv_write(gpu):
     assert int((kc3 != 0).sum()) == int((kc3[b3, :, o3, :] != 0).sum())
 
 
+# The attention tests below draw q, k and v ~ N(0, 1): they cover layouts, masks at the end of a context, GQA and
+# RoPE at load, but with such scores the online softmax never rescales a non-empty accumulator, and 2e-2 cannot
+# see one wrong key among 200.  tests/test_attention_probes_gpu.py runs the same entry points on structured
+# scores (staircases, spikes on every edge key, exact flat rows); tests/test_attention_probes.py shows what
+# those comparisons reject.  A change to an attention kernel wants both files green.
+
+
 @pytest.fixture(params=["wg4", "wave"])
 def decode_path(request, gpu):
     """Run a decode test through the 4-waves-per-sequence kernel and the wave-per-item kernel."""
