@@ -40,7 +40,9 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import blas_tuning, gemm_plan
+from . import step_plan
 from .config import DecoderConfig
+from .step_plan import ChainPlan
 
 
 def rope_tables(cfg: DecoderConfig, device, max_pos: Optional[int] = None):
@@ -161,7 +163,7 @@ class LlamaModel:
         self.extra_bytes = 0  # device bytes the folded norms add (a tied lm_head's own copy)
         self.final_norm_weight: Optional[torch.Tensor] = None  # the final norm's weight once lm_head holds it
         self.chain: Optional[ops.NormChain] = None
-        self.chain_m: dict = {}  # decode batch M -> (use the chain, qkv tile width)
+        self.chain_m: dict = {}  # decode batch M -> the step's chain plan, as a dict (step_plan.ChainPlan.from_dict)
         self.lora = None
         if lora is not None:
             from .lora import LoraSet
@@ -296,8 +298,8 @@ class LlamaModel:
         ``mode``: "own32" / "own64" — gemm4w's residual epilogue writes them (RS 2, schedule 32 / 64);
         "sumsq" — the planner's residual GEMM, then one rms_rowsumsq pass; "plain" — no partials (the next
         consumer normalises with the norm kernel)."""
-        if mode in ("own32", "own64"):
-            ops.gemm4w(inp, w, residual=x_res, out=x_res, chain=self.chain, var=32 if mode == "own32" else 64)
+        if mode in step_plan.OWN_VAR:
+            ops.gemm4w(inp, w, residual=x_res, out=x_res, chain=self.chain, var=step_plan.OWN_VAR[mode])
             return
         gemm_plan.linear_add_(inp, w, x_res, ws=self.g8_ws)
         if mode == "sumsq":
@@ -305,41 +307,40 @@ class LlamaModel:
 
     def _chain_layers(self, x_res: torch.Tensor, cache: KVCache, positions, slots, attn_fn, rope_q: bool,
                       plan: dict) -> torch.Tensor:
-        """Decode layers + lm_head with the folded norms per ``plan`` (:meth:`_tune_chain`): at each norm point
-        ("attn": qkv, "mlp": gate|up, "final": lm_head) either the consumer scales its rows from the chain's
+        """Decode layers + lm_head with the folded norms per ``plan`` (a :class:`ChainPlan` dict): at each norm
+        point ("attn": qkv, "mlp": gate|up, "final": lm_head) either the consumer scales its rows from the chain's
         partials ("fold") or the norm kernel (weights ones: the norms are in the projections) runs first;
-        the producers of folded points leave partials by ``plan["o"]`` / ``plan["down"]``.  Returns logits."""
+        the producers of folded points leave partials by the plan's live ``o`` / ``down`` mode.  Returns logits."""
         cfg, ch = self.cfg, self.chain
         T = x_res.shape[0]
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
         ones, eps = self.final_norm, cfg.rms_eps  # (every norm weight is ones after folding)
-        if plan["attn"]:
+        p = ChainPlan.from_dict(plan).live()
+        if p.attn:
             ops.rms_rowsumsq(x_res, ch)
         nl = len(self.layers)
-        qv, gv, lv = plan.get("qkv_var", 32), plan.get("gu_var", 32), plan.get("lm_var", 32)
         for li, L in enumerate(self.layers):
-            if plan["attn"]:
-                qkv = ops.gemm4w(x_res, L.wqkv, bn=plan["qkv_bn"], chain=ch, var=qv)
+            if p.attn:
+                qkv = ops.gemm4w(x_res, L.wqkv, bn=p.qkv_bn, chain=ch, var=p.qkv_var)
             else:
                 qkv = self._proj(ops.rmsnorm(x_res, ones, eps), L.wqkv)
             self._rope_kv_write(qkv, L, positions, cache.k[li], cache.v[li], slots, rope_q)
             attn = attn_fn(qkv, li).reshape(T, Hq * D)
-            self._residual_into(attn, L.wo, x_res, plan["o"] if plan["mlp"] else "plain")
-            if plan["mlp"]:
-                act = ops.gemm4w(x_res, L.w_gate_up, swiglu=True, chain=ch, var=gv)
+            self._residual_into(attn, L.wo, x_res, p.o)
+            if p.mlp:
+                act = ops.gemm4w(x_res, L.w_gate_up, swiglu=True, chain=ch, var=p.gu_var)
             else:
                 act = gemm_plan.swiglu(ops.rmsnorm(x_res, ones, eps), L.w_gate_up, L.gu_block, ws=self.g8_ws)
-            nxt = plan["attn"] if li + 1 < nl else plan["final"]
-            self._residual_into(act, L.w_down, x_res, plan["down"] if nxt else "plain")
-        if plan["final"]:
-            sk = ops.split_plan(T, self.lm_head.shape[0], cfg.hidden) if plan.get("lm_split") and lv == 64 else (1, 0)
-            return ops.gemm4w(x_res, self.lm_head, chain=ch, var=lv, splits=sk[0], split_from=sk[1])
+            self._residual_into(act, L.w_down, x_res, p.down_mode(last=li + 1 == nl))
+        if p.final:
+            sk = ops.split_plan(T, self.lm_head.shape[0], cfg.hidden) if p.lm_split else (1, 0)
+            return ops.gemm4w(x_res, self.lm_head, chain=ch, var=p.lm_var, splits=sk[0], split_from=sk[1])
         return self._proj(ops.rmsnorm(x_res, ones, eps), self.lm_head)
 
     def chain_ok(self, M: int) -> bool:
         """Whether a decode step of M rows folds at least one norm (timed faster at M, before capture)."""
         c = self.chain_m.get(M)
-        return bool(c and (c["attn"] or c["mlp"] or c["final"])) and self.chain is not None and M <= self.chain.max_rows
+        return bool(c) and ChainPlan.from_dict(c).folds and self.chain is not None and M <= self.chain.max_rows
 
     def _layers(self, x_res: torch.Tensor, cache: KVCache, positions, slots, attn_fn, rope_q: bool = True,
                 keep: Optional[torch.Tensor] = None, final_norm: Optional[torch.Tensor] = None,
@@ -498,6 +499,24 @@ class LlamaModel:
     def comm_poll(self) -> None:
         """Tensor-parallel subclasses raise here once a failed collective is visible on the host."""
 
+    @property
+    def _planned_gemms(self) -> bool:
+        """Whether the projections go through ops/gemm_plan.py (the dense bf16 decoder on the GPU)."""
+        return self.g8_ws is not None and isinstance(self.layers[0], LayerWeights) and not self.fp8_dense
+
+    def _chain_unusable(self, M: int) -> Optional[str]:
+        """Why a decode step of M rows cannot fold norms, or None when it can; the NormChain is allocated here,
+        once for every decode bucket (captured graphs keep its addresses)."""
+        if not self._planned_gemms:
+            return "this model runs no planned GEMMs"
+        if not self.norm_folded:
+            return "the model's norms are not folded"
+        if self.chain is None:
+            self.chain = ops.NormChain(max(M, 8192), self.cfg.hidden, self.cfg.rms_eps, self.device)
+        if M > self.chain.max_rows:
+            return f"the norm chain holds {self.chain.max_rows} rows"
+        return None
+
     def tune_gemms(self, M: int, bucket: bool = False, lm_head: bool = True, only=None) -> None:
         """Pick the GEMM backend of every decode projection at batch M by timing both (before the
         bucket's hipGraph is captured; see ops/gemm_plan.py).  ``bucket``: M is a row-count bucket of the
@@ -507,7 +526,7 @@ class LlamaModel:
         if M in self.pinned and not bucket and only is None:
             self._apply_pinned(M)
             return
-        if self.g8_ws is None or not isinstance(self.layers[0], LayerWeights) or self.fp8_dense:
+        if not self._planned_gemms:
             return
         cfg, L = self.cfg, self.layers[0]
         if only is not None:
@@ -530,44 +549,37 @@ class LlamaModel:
 
     def pin_step_plan(self, M: int, plan: dict) -> None:
         """Fix the decode step's plan at batch M (the form of :meth:`step_plans`' entries: ``choices`` per
-        projection, ``chain`` for the folded norms): :meth:`tune_gemms` and the engine's in-step A/B then time
-        nothing at M, so every run of the process executes the same kernels and computes the same values
-        (timed choices flip between near-equal candidates from run to run)."""
+        projection, ``chain`` for the folded norms; ValueError for a plan that does not parse):
+        :meth:`tune_gemms` and the engine's in-step A/B then time nothing at M, so every run of the process
+        executes the same kernels and computes the same values (timed choices flip between near-equal
+        candidates from run to run)."""
+        step_plan.check_plan(plan)
         self.pinned[M] = {"choices": dict(plan["choices"]), "chain": dict(plan["chain"]) if plan.get("chain") else None}
 
     def _apply_pinned(self, M: int) -> None:
         plan = self.pinned[M]
-        if self.g8_ws is None or not isinstance(self.layers[0], LayerWeights) or self.fp8_dense:
+        if not self._planned_gemms:
             raise RuntimeError(f"a decode plan is pinned at batch {M}, but this model runs no planned GEMMs")
-        ch = plan["chain"]
-        if ch is not None and (ch["attn"] or ch["mlp"] or ch["final"]):
-            if not self.norm_folded:
-                raise RuntimeError(f"the plan pinned at batch {M} folds norms, but the model's norms are not folded")
-            if self.chain is None:  # as in _tune_chain: once, for every decode bucket
-                self.chain = ops.NormChain(max(M, 8192), self.cfg.hidden, self.cfg.rms_eps, self.device)
-            if M > self.chain.max_rows:
-                raise RuntimeError(f"the plan pinned at batch {M} exceeds the norm chain's {self.chain.max_rows} rows")
+        if plan["chain"] is not None and ChainPlan.from_dict(plan["chain"]).folds:
+            why = self._chain_unusable(M)
+            if why is not None:
+                raise RuntimeError(f"the plan pinned at batch {M} folds norms, but {why}")
         self.apply_step_plan(M, plan)
 
     def _tune_chain(self, M: int, x, xa, xf) -> None:
         """Decode batch M: decide, per norm point, between the norm kernel + the best projection backend and the
         folded norm (the consumer's row-scaled gemm4w, the producer leaving partial row sums of squares by its
-        own residual epilogue or by one rms_rowsumsq pass after the planner's GEMM).  Every candidate is
-        timed alone (interleaved rounds, median), the plan is the cheaper side at each point and is recorded
-        in ``chain_m`` (``LWC_NORM_CHAIN=0|1`` forces all-unfolded / all-folded)."""
+        own residual epilogue or by one rms_rowsumsq pass after the planner's GEMM).  Every candidate
+        (``step_plan.CHAIN_CANDIDATES``) is timed alone (interleaved rounds, median), the plan is the cheaper
+        side at each point and is recorded in ``chain_m`` (``LWC_NORM_CHAIN=0|1`` forces all-unfolded /
+        all-folded)."""
         if M in self.chain_m or torch.cuda.is_current_stream_capturing():
             return
         cfg, L = self.cfg, self.layers[0]
-        none = {"attn": False, "mlp": False, "final": False, "qkv_bn": 192, "o": "plain", "down": "plain"}
         # below 256 rows the chain's 256-row tiles run mostly empty and the weight-streaming cores win every
         # projection: not timed (a serving engine meets many such buckets)
-        if (cfg.hidden + 255) // 256 > 16 or M < 256:
-            self.chain_m[M] = none
-            return
-        if self.chain is None:  # once, for every decode bucket (captured graphs keep these addresses)
-            self.chain = ops.NormChain(max(M, 8192), cfg.hidden, cfg.rms_eps, self.device)
-        if M > self.chain.max_rows:
-            self.chain_m[M] = none
+        if (cfg.hidden + 255) // 256 > 16 or M < 256 or self._chain_unusable(M) is not None:
+            self.chain_m[M] = ChainPlan.UNFOLDED.as_dict()
             return
         ch, eps = self.chain, cfg.rms_eps
         x_res = x.clone()
@@ -575,6 +587,8 @@ class LlamaModel:
         ops.rms_rowsumsq(x_res, ch)  # valid partials for the row-scaled candidates
         P0 = ch.P
         w = {"qkv": L.wqkv, "o": L.wo, "gu": L.w_gate_up, "down": L.w_down, "lm": self.lm_head}
+        cands = step_plan.CHAIN_CANDIDATES
+        lm_sk = ops.split_plan(M, self.lm_head.shape[0], cfg.hidden)  # lm_head's ragged last round, split
 
         def fold(name, **kw):
             def run():
@@ -582,32 +596,29 @@ class LlamaModel:
                 ops.gemm4w(x, w[name], chain=ch, **kw)
             return run
 
-        # the row-scaled consumers at both schedules (VAR 32: block-staged epilogue; 64: wave-local, next tile
-        # prefetched) and, for qkv, both tile widths
-        cons = {"qkv": {f"qkv_rs{bn}v{v}": (bn, v) for bn in (192, 256) for v in (32, 64)},
-                "gu": {f"gu_rsv{v}": (256, v) for v in (32, 64)},
-                "lm": {f"lm_rsv{v}": (256, v) for v in (32, 64)}}
-        lm_sk = ops.split_plan(M, self.lm_head.shape[0], cfg.hidden)  # lm_head's ragged last round, split
-
-        def res(name, inp, var):
-            return lambda: ops.gemm4w(inp, w[name], residual=x_res, out=x_res, chain=ch, var=var)
+        def own(name, inp):  # the producer's own epilogue at both schedules
+            def res(var):
+                return lambda: ops.gemm4w(inp, w[name], residual=x_res, out=x_res, chain=ch, var=var)
+            return {c: res(step_plan.OWN_VAR[f[name]]) for c, f in cands[name].items()}
 
         runs = {
             "norm": lambda: ops.rmsnorm(x_res, ones, eps),
             "sumsq": lambda: ops.rms_rowsumsq(x_res, ch),
             "qkv": lambda: self._proj(x, L.wqkv),
-            "o": lambda: gemm_plan.linear_add_(xa, L.wo, x_res, ws=self.g8_ws),
-            "o_own32": res("o", xa, 32), "o_own64": res("o", xa, 64),
+            "o": lambda: gemm_plan.linear_add_(xa, L.wo, x_res, ws=self.g8_ws), **own("o", xa),
             "gu": lambda: gemm_plan.swiglu(x, L.w_gate_up, L.gu_block, ws=self.g8_ws),
-            "down": lambda: gemm_plan.linear_add_(xf, L.w_down, x_res, ws=self.g8_ws),
-            "down_own32": res("down", xf, 32), "down_own64": res("down", xf, 64),
+            "down": lambda: gemm_plan.linear_add_(xf, L.w_down, x_res, ws=self.g8_ws), **own("down", xf),
             "lm": lambda: self._proj(x, self.lm_head),
         }
-        for pt, cands in cons.items():
-            for k, (bn, v) in cands.items():
-                runs[k] = fold(pt, bn=bn, var=v, swiglu=pt == "gu")
-        if lm_sk[0] > 1:
-            runs["lm_rsv64s"] = fold("lm", bn=256, var=64, splits=lm_sk[0], split_from=lm_sk[1])
+        # the row-scaled consumers at both schedules (VAR 32: block-staged epilogue; 64: wave-local, next tile
+        # prefetched), for qkv both tile widths, for lm_head the split tail where there is one
+        for pt in ("qkv", "gu", "lm"):
+            for c, f in cands[pt].items():
+                if f.get("lm_split"):
+                    if lm_sk[0] > 1:
+                        runs[c] = fold(pt, bn=256, var=f["lm_var"], splits=lm_sk[0], split_from=lm_sk[1])
+                else:
+                    runs[c] = fold(pt, bn=f.get("qkv_bn", 256), var=f[f"{pt}_var"], swiglu=pt == "gu")
         ts = {k: [] for k in runs}
         for _ in range(3):  # interleaved rounds (one process, one device: matched clocks and caches)
             for k, fn in runs.items():
@@ -618,42 +629,46 @@ class LlamaModel:
         def producer(name):  # the cheapest way to leave partials, and its cost over the plain residual GEMM
             # (isolated timings; the engine's in-step A/B of whole captured decode steps then decides between
             # this plan, the all-library one and the all-own one: LlamaModel.step_plans)
-            opts = {"own32": t[f"{name}_own32"], "own64": t[f"{name}_own64"], "sumsq": t[name] + t["sumsq"]}
-            best = min(opts, key=opts.get)
-            return best, opts[best] - t[name]
-
-        def consumer(pt):
-            k = min(cons[pt], key=lambda c: t[c])
-            return k, cons[pt][k]
-
-        lm_split = "lm_rsv64s" in t and t["lm_rsv64s"] < min(t["lm_rsv32"], t["lm_rsv64"])
+            costs = step_plan.producer_costs(name, t)
+            best = min(costs, key=costs.get)
+            return best, costs[best] - t[name]
 
         o_mode, o_extra = producer("o")
         d_mode, d_extra = producer("down")
-        (qk, (qkv_bn, qv)), (gk, (_, gv)), (lk, (_, lv)) = consumer("qkv"), consumer("gu"), consumer("lm")
+        qk, gk, lk = (step_plan.fastest_candidate(pt, t) for pt in ("qkv", "gu", "lm"))
         # each point: folded (consumer + producer's extra) vs the norm kernel + the consumer's best backend
         attn = t[qk] + d_extra < t["norm"] + t["qkv"]
         mlp = t[gk] + o_extra < t["norm"] + t["gu"]
-        if lm_split:
-            lk, lv = "lm_rsv64s", 64
         final = t[lk] + d_extra < t["norm"] + t["lm"]
         force = os.environ.get("LWC_NORM_CHAIN")
         if force is not None:
             attn = mlp = final = force == "1"
-        plan = {"attn": attn, "mlp": mlp, "final": final, "qkv_bn": qkv_bn, "qkv_var": qv, "gu_var": gv,
-                "lm_var": lv, "lm_split": lm_split, "o": o_mode, "down": d_mode}
+        plan = ChainPlan(attn=attn, mlp=mlp, final=final, **cands["qkv"][qk], **cands["gu"][gk], **cands["lm"][lk],
+                         o=o_mode, down=d_mode).as_dict()
         self.chain_m[M] = plan
         key = (M, cfg.hidden, 0, "norm_chain")
         gemm_plan.TIMINGS[key] = t
         gemm_plan._CHOICE[key] = ",".join(f"{k}={v}" for k, v in plan.items())
 
     # ------------------------------------------------------------------ whole-step plans (engine in-step A/B)
+    # (thin wrappers: the planner's recorded state goes in, models/step_plan.py decides)
     def _plan_keys(self, M: int) -> dict:
         cfg = self.cfg
         epi = "residual" if self._dense_residual else "plain"
         return {"qkv": (M, cfg.qkv_dim, cfg.hidden, "plain"), "o": (M, cfg.hidden, cfg.heads * cfg.head_dim, epi),
                 "gu": (M, 2 * cfg.ffn, cfg.hidden, "swiglu"), "down": (M, cfg.hidden, cfg.ffn, epi),
                 "lm": (M, cfg.vocab_size, cfg.hidden, "plain")}
+
+    def _own_backends(self, M: int) -> dict:
+        """Each projection's fastest hand-written backend by the planner's timings at M (None: none timed)."""
+        own = {}
+        for n, k in self._plan_keys(M).items():
+            t = {b: v for b, v in gemm_plan.TIMINGS.get(k, {}).items() if b != "blas" and isinstance(v, float)}
+            own[n] = min(t, key=t.get) if t else None
+        return own
+
+    def _chain_timings(self, M: int) -> Optional[dict]:
+        return gemm_plan.TIMINGS.get((M, self.cfg.hidden, 0, "norm_chain"))
 
     def step_plans(self, M: int) -> dict:
         """Candidate plans for a decode step of M rows, for the engine's in-step A/B (it captures the decode
@@ -665,86 +680,22 @@ class LlamaModel:
         keys = self._plan_keys(M)
         if self.g8_ws is None or not any(k in gemm_plan._CHOICE for k in keys.values()):
             return {}
-        plans = {"planner": {"choices": {n: gemm_plan._CHOICE.get(k) for n, k in keys.items()},
-                             "chain": self.chain_m.get(M)}}
-        none = {"attn": False, "mlp": False, "final": False, "qkv_bn": 192, "o": "plain", "down": "plain"}
-        plans["library"] = {"choices": {n: "blas" for n in keys}, "chain": none if M in self.chain_m else None}
-        own = {}
-        for n, k in keys.items():
-            t = {b: v for b, v in gemm_plan.TIMINGS.get(k, {}).items() if b != "blas" and isinstance(v, float)}
-            own[n] = min(t, key=t.get) if t else gemm_plan._CHOICE.get(k)
-        chain = self.chain_m.get(M)
-        t = gemm_plan.TIMINGS.get((M, self.cfg.hidden, 0, "norm_chain"))
-        if chain is not None and t:
-            def best(cands):
-                return min(cands, key=lambda c: t.get(c, float("inf")))
-            q = best([f"qkv_rs{bn}v{v}" for bn in (192, 256) for v in (32, 64)])
-            lm = best(["lm_rsv32", "lm_rsv64", "lm_rsv64s"])
-            chain = {"attn": True, "mlp": True, "final": True, "qkv_bn": int(q[6:9]), "qkv_var": int(q[10:]),
-                     "gu_var": int(best(["gu_rsv32", "gu_rsv64"])[6:]), "lm_var": int(lm[6:8]),
-                     "lm_split": lm.endswith("s"), "o": best(["o_own32", "o_own64"])[2:],
-                     "down": best(["down_own32", "down_own64"])[5:]}
-        plans["own"] = {"choices": own, "chain": chain}
-        return plans
+        return step_plan.step_plans({n: gemm_plan._CHOICE.get(k) for n, k in keys.items()}, self._own_backends(M),
+                                    self.chain_m.get(M), self._chain_timings(M))
 
     def step_moves(self, M: int, plan: dict) -> list:
         """Single-decision changes of ``plan`` (the engine's coordinate-descent A/B, after the whole-plan
         round): each projection's backend (hipBLASLt <-> its fastest hand-written core) where the norm chain
         does not own it, each norm point folded or not, the consumers' schedule / tile width, the producers'
         mode.  [(label, delta)]: ``with_move(plan, delta)`` applies one."""
-        keys = self._plan_keys(M)
-        own = {}
-        for n, k in keys.items():
-            t = {b: v for b, v in gemm_plan.TIMINGS.get(k, {}).items() if b != "blas" and isinstance(v, float)}
-            own[n] = min(t, key=t.get) if t else None
-        ch = plan.get("chain")
-        owned = set()
-        if ch is not None and self.chain is not None and M <= self.chain.max_rows:
-            owned = {n for n, pt in (("qkv", "attn"), ("gu", "mlp"), ("lm", "final")) if ch.get(pt)}
-            if ch.get("mlp") and ch.get("o") in ("own32", "own64"):
-                owned.add("o")
-            if (ch.get("attn") or ch.get("final")) and ch.get("down") in ("own32", "own64"):
-                owned.add("down")
-        moves = []
+        usable = self.chain is not None and M <= self.chain.max_rows
+        return step_plan.step_moves(plan, self._own_backends(M), usable, self._chain_timings(M))
 
-        def variant(label, choices=None, chain=None):
-            moves.append((label, {"choices": dict(choices or {}), "chain": dict(chain or {})}))
-
-        for n in keys:
-            c = plan["choices"].get(n)
-            if n in owned or own[n] is None:
-                continue
-            variant(f"{n}={'blas' if c != 'blas' else own[n]}", {n: "blas" if c != "blas" else own[n]})
-        if ch is not None and self.chain is not None and M <= self.chain.max_rows:
-            for pt in ("attn", "mlp", "final"):
-                variant(f"{pt}_fold={not ch.get(pt)}", chain={pt: not ch.get(pt)})
-            # (only moves that change the step: a consumer's schedule / tile width where its norm point is
-            # folded, a producer's mode where a folded point reads it — plan_summary's rules.  A no-op move
-            # once "won" by 0.3 % of replay noise)
-            if ch.get("final"):
-                variant(f"lm_split={not ch.get('lm_split', False)}", chain={"lm_split": not ch.get("lm_split", False),
-                                                                            "lm_var": 64})
-            for key, pt, alts in (("qkv_var", "attn", (32, 64)), ("gu_var", "mlp", (32, 64)),
-                                  ("lm_var", "final", (32, 64)), ("qkv_bn", "attn", (192, 256))):
-                cur = ch.get(key, alts[0])
-                for v in alts:
-                    if v != cur and ch.get(pt):
-                        variant(f"{key}={v}", chain={key: v})
-            for key, live in (("o", ch.get("mlp")), ("down", ch.get("attn") or ch.get("final"))):
-                for v in ("own32", "own64", "sumsq"):
-                    if v != ch.get(key) and live:
-                        variant(f"{key}_producer={v}", chain={key: v})
-        return moves
-
-    @staticmethod
-    def with_move(plan: dict, delta: dict) -> dict:
-        """``plan`` with one :meth:`step_moves` delta applied (choices and chain entries overridden)."""
-        ch = plan.get("chain")
-        return {"choices": dict(plan["choices"], **delta.get("choices", {})),
-                "chain": dict(ch, **delta.get("chain", {})) if ch is not None else None}
+    with_move = staticmethod(step_plan.with_move)
 
     def apply_step_plan(self, M: int, plan: dict) -> None:
         """Make ``plan`` (one of :meth:`step_plans`) the choice of every projection at M (and of the norm chain)."""
+        step_plan.check_plan(plan)
         keys = self._plan_keys(M)
         for n, c in plan["choices"].items():
             if c is not None:
@@ -754,21 +705,8 @@ class LlamaModel:
 
     def plan_summary(self, M: int) -> dict:
         """The kernels a decode step of M rows runs, compactly (bench JSON / logs)."""
-        keys = self._plan_keys(M)
-        out = {n: gemm_plan._CHOICE.get(k, "blas") for n, k in keys.items()}
-        c = self.chain_m.get(M)
-        if c and self.chain_ok(M):
-            if c["attn"]:
-                out["qkv"] = f"g4 rs{c['qkv_bn']} v{c.get('qkv_var', 32)}"
-            if c["mlp"]:
-                out["gu"] = f"g4 rs v{c.get('gu_var', 32)}"
-            if c["final"]:
-                out["lm"] = f"g4 rs v{c.get('lm_var', 32)}" + (" split-K tail" if c.get("lm_split") else "")
-            if c["mlp"] and c["o"] != "plain":
-                out["o"] = out["o"] + "+sumsq" if c["o"] == "sumsq" else f"g4 rs2 v{c['o'][3:]}"
-            if (c["attn"] or c["final"]) and c["down"] != "plain":
-                out["down"] = out["down"] + "+sumsq" if c["down"] == "sumsq" else f"g4 rs2 v{c['down'][3:]}"
-        return out
+        backends = {n: gemm_plan._CHOICE.get(k, "blas") for n, k in self._plan_keys(M).items()}
+        return step_plan.plan_summary(backends, ChainPlan.from_dict(self.chain_m[M]) if self.chain_ok(M) else None)
 
     def decode(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, block_tables: torch.Tensor,
                ctx_lens: torch.Tensor, cache: KVCache, num_splits: int = 1,

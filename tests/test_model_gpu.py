@@ -347,6 +347,57 @@ def test_folded_norm_chain_matches_unfolded(tiny, gpu, qkv_bn):
     assert _cos(got[B - 1], ref_logits[P]) > 0.995 and _cos(got[0], ref_logits[P]) > 0.995
 
 
+def test_fold_moves_from_library_plan_bring_their_producer(tiny, gpu):
+    """The engine's single-decision moves from the all-library plan (nothing folded, o / down "plain"): folding
+    one norm point must also make its producer leave the partial row sums of squares, or the row-scaled GEMM
+    reads whatever the chain's buffer held.  The buffer is poisoned (1e30: row scales near 0) before every
+    decode; each folded step must equal the unfolded one, B = 300 as in the test above."""
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.llama import KVCache
+    from llm_weighted_consensus_amd.ops import gemm_plan
+
+    m = tiny
+    cache = KVCache(m.cfg, 64, 16, gpu)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    toks = torch.randint(0, m.cfg.vocab_size, (36,), generator=g).to(gpu)
+    P = 35
+    pos = torch.arange(P, dtype=torch.int32, device=gpu)
+    m.prefill(toks[:P].int(), pos, pos.clone(), torch.tensor([0, P], dtype=torch.int32, device=gpu), P,
+              torch.tensor([P - 1], device=gpu), cache)
+    B = 300
+
+    def full(v):
+        return torch.full((B,), v, dtype=torch.int32, device=gpu)
+
+    bt = torch.arange(4, dtype=torch.int32, device=gpu).view(1, 4).expand(B, 4).contiguous()
+    args = (toks[P:P + 1].int().expand(B).contiguous(), full(P), full(P), bt, full(P + 1), cache)
+    if m.chain is None:
+        m.chain = ops.NormChain(8192, m.cfg.hidden, m.cfg.rms_eps, gpu)
+    saved, choices = dict(m.chain_m), dict(gemm_plan._CHOICE)
+    try:
+        for k in m._plan_keys(B).values():  # the planner's state at B, as recorded without timing anything
+            gemm_plan._CHOICE[k] = "blas"
+        m.chain_m[B] = {"attn": False, "mlp": False, "final": False, "qkv_bn": 192, "o": "plain", "down": "plain"}
+        lib = m.step_plans(B)["library"]
+        moves = {lb: dl for lb, dl in m.step_moves(B, lib) if lb.endswith("_fold=True")}
+        assert sorted(moves) == ["attn_fold=True", "final_fold=True", "mlp_fold=True"]
+        outs = {}
+        for lb, plan in [("library", lib)] + [(lb, m.with_move(lib, dl)) for lb, dl in moves.items()]:
+            m.apply_step_plan(B, plan)
+            assert m.chain_ok(B) == (lb != "library")
+            m.chain.ss.fill_(1e30)
+            outs[lb] = m.decode(*args, num_splits=1).float()
+    finally:
+        m.chain_m.clear()
+        m.chain_m.update(saved)
+        gemm_plan._CHOICE.clear()
+        gemm_plan._CHOICE.update(choices)
+    base = outs.pop("library")
+    for lb, got in outs.items():
+        assert _cos(got, base) > 0.9995, lb
+        assert (got - base).abs().max() < 0.05 * base.abs().max(), lb
+
+
 def test_pinned_step_plan_runs_untimed_and_repeats(gpu, monkeypatch):
     """LlamaModel.pin_step_plan: at the pinned batch neither tune_gemms nor the engine's in-step A/B times
     anything, the decode step runs exactly the pinned kernels (here the whole folded norm chain), and two fresh
