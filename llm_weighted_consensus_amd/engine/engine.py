@@ -44,6 +44,7 @@ from ..utils.tracing import RequestTimer, span
 from .._runtime import BlockManager, prepare_decode_into, slots_range
 from ..models.llama import KVCache
 from .sampling import SamplingParams
+from .staging import PackedLayout, SamplerBatch, _h2d, output_layout, row_segments, unpack_outputs
 from .tokenizer import IncrementalDecoder
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1024, 1536, 2048, 3072, 4096, 5120, 6144, 8192)
@@ -131,74 +132,40 @@ class SequenceGroup:
         return all(s.finished for s in self.seqs)
 
 
-_F32_PARAMS = ("temperature", "top_p", "min_p", "top_a", "freq_pen", "pres_pen", "rep_pen")
-_I32_PARAMS = ("top_k", "count_rows", "bias_rows", "lora_ids")
-
-
 class _GraphBucket:
     """Per batch-size bucket: the captured decode graph plus ONE int32 staging layout holding every
     per-step input (block tables, ctx lens, slots, positions, tokens, prefix tiles, sampler
     parameters, each row's LoRA adapter index, Philox seeds/offsets).  The host side is two pinned buffers
-    (alternating steps), the
-    device side one buffer whose views are the graph's inputs, so a step is one H2D copy."""
+    (alternating steps), the device side one buffer whose views are the graph's inputs, so a step is one H2D copy."""
 
     def __init__(self, B: int, width: int, splits: int, max_tiles: int, device):
         self.B, self.width, self.splits, self.max_tiles = B, width, splits, max_tiles
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.logits: Optional[torch.Tensor] = None
         # captured decode graphs by attention mode (True = cascade, False = plain split-K), sharing one
         # memory pool, and their output logits
         self.graphs: Dict[bool, torch.cuda.CUDAGraph] = {}
         self.graph_logits: Dict[bool, torch.Tensor] = {}
         self.pool = None
-        segs: List[Tuple[str, int]] = [("block_tables", B * width), ("ctx_lens", B), ("slots", B), ("positions", B),
-                                       ("tokens", B), ("tiles", max(1, max_tiles) * 3)]
-        segs += [(n, B) for n in _F32_PARAMS + _I32_PARAMS]
-        segs += [("seeds", 2 * B), ("offsets", 2 * B)]
-        self.off: Dict[str, Tuple[int, int]] = {}
-        o = 0
-        for name, n in segs:
-            o += o & 1  # keep every segment 8-byte aligned (int64 views)
-            self.off[name] = (o, o + n)
-            o += n
-        self.size = o + (o & 1)
-        self.dev = torch.zeros(self.size, dtype=torch.int32, device=device)
-        self.host = [torch.zeros(self.size, dtype=torch.int32).pin_memory() for _ in range(2)]
+        lay = PackedLayout([("block_tables", (B, width), np.int32)]
+                           + [(name, B, np.int32) for name in ("ctx_lens", "slots", "positions", "tokens")]
+                           + [("tiles", (max(1, max_tiles), 3), np.int32)] + row_segments(B))
+        self.dev = torch.zeros(lay.size, dtype=torch.int32, device=device)
+        self.host = [torch.zeros(lay.size, dtype=torch.int32).pin_memory() for _ in range(2)]
         self.host_static_key: List[object] = [None, None]
-        self.d = self._views(self.dev, torch)
-        self.h = [self._views(h.numpy(), np) for h in self.host]
+        self.d = lay.views(self.dev)
+        self.h = [lay.views(h.numpy()) for h in self.host]
         self.out_dev: List[Optional[torch.Tensor]] = [None, None]
         self.out_host: List[Optional[torch.Tensor]] = [None, None]
 
-    def _views(self, buf, lib):
-        f32 = torch.float32 if lib is torch else np.float32
-        i64 = torch.int64 if lib is torch else np.int64
-        v = {}
-        for name, (a, b) in self.off.items():
-            x = buf[a:b]
-            if name in _F32_PARAMS:
-                x = x.view(f32)
-            elif name in ("seeds", "offsets"):
-                x = x.view(i64)
-            v[name] = x
-        v["block_tables"] = v["block_tables"].reshape(self.B, self.width)
-        v["tiles"] = v["tiles"].reshape(max(1, self.max_tiles), 3)
-        return v
-
     def outputs(self, parity: int, K: int):
-        """Sampler outputs for one step as views of one device buffer (tok | lp | topk ids | topk lp),
+        """Sampler outputs for one step as views of one device buffer (:func:`staging.output_layout`),
         and the matching pinned host buffer (one D2H copy per step)."""
-        B, Kb = self.B, max(K, 1)
-        need = B * (2 + 2 * Kb)
-        if self.out_dev[parity] is None or self.out_dev[parity].numel() < need:
-            self.out_dev[parity] = torch.empty(need, dtype=torch.int32, device=self.dev.device)
-            self.out_host[parity] = torch.empty(need, dtype=torch.int32).pin_memory()
-        o = self.out_dev[parity]
-        tok = o[:B]
-        lp = o[B:2 * B].view(torch.float32)
-        ids = o[2 * B:2 * B + B * Kb].view(B, Kb)
-        lps = o[2 * B + B * Kb:need].view(torch.float32).view(B, Kb)
-        return (tok, lp, ids, lps), o[:need], self.out_host[parity][:need]
+        lay = output_layout(self.B, K)
+        if self.out_dev[parity] is None or self.out_dev[parity].numel() < lay.size:
+            self.out_dev[parity] = torch.empty(lay.size, dtype=torch.int32, device=self.dev.device)
+            self.out_host[parity] = torch.empty(lay.size, dtype=torch.int32).pin_memory()
+        o = self.out_dev[parity][:lay.size]
+        return tuple(lay.views(o).values()), o, self.out_host[parity][:lay.size]
 
 
 def cascade_table_size(B: int, per_tile: int) -> int:
@@ -257,67 +224,28 @@ def cascade_tiles(runs: List[Tuple[int, int, int]], per_tile: int, tiles: np.nda
     return nt
 
 
-class _PinnedRing:
-    """Pinned host staging for the engine's per-step uploads: one pinned arena used as a ring.  An upload
-    copies into the next free region and issues a non-blocking copy from it; a region is written again only
-    after the event recorded behind its upload completed (oldest first, the ring's own order).  A fresh
-    ``pin_memory()`` per upload cost ~250 us of host time each (~15 per mixed step; serve_load cProfile)."""
-
-    def __init__(self, nbytes: int = 32 << 20):
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        self.n, self.head = nbytes, 0
-        self.live: Deque[Tuple[int, int, "torch.cuda.Event"]] = deque()
-
-    def upload(self, t: torch.Tensor, dev) -> torch.Tensor:
-        nb = t.numel() * t.element_size()
-        size = (nb + 255) & ~255
-        if size > self.n // 4:
-            return t.pin_memory().to(dev, non_blocking=True)
-        if self.head + size > self.n:
-            self.head = 0
-        start, end = self.head, self.head + size
-        while self.live and self.live[0][0] < end and start < self.live[0][1]:
-            self.live.popleft()[2].synchronize()  # (regions are handed out in order: the oldest overlaps first)
-        self.head = end
-        dst = self.buf[start:start + nb].view(t.dtype).view(t.shape)
-        dst.copy_(t)
-        out = dst.to(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.live.append((start, end, ev))
-        if len(self.live) > 4096:  # bounded bookkeeping: retire the oldest
-            self.live.popleft()[2].synchronize()
-        return out
+def _group_runs(seqs: List[Sequence]):
+    """The batch's runs of consecutive sequences of one group, as (start, count, group)."""
+    i = 0
+    for _, run in itertools.groupby(seqs, key=lambda s: id(s.group)):
+        n = len(list(run))
+        yield i, n, seqs[i].group
+        i += n
 
 
-_RINGS = threading.local()
-
-
-def _h2d(x, dtype, dev) -> torch.Tensor:
-    """Host list / array -> device through pinned memory, non-blocking: a pageable upload synchronises
-    the stream, i.e. would hold the host until every queued kernel (a decode step in flight) finished.
-    Staged through this thread's pinned ring (one per engine thread and device)."""
-    t = (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.tensor(x)).to(dtype)
-    dev = torch.device(dev)
-    if dev.type != "cuda":
-        return t.to(dev)
-    rings = getattr(_RINGS, "by_dev", None)
-    if rings is None:
-        rings = _RINGS.by_dev = {}
-    ring = rings.get(dev)
-    if ring is None:
-        ring = rings[dev] = _PinnedRing()
-    return ring.upload(t.contiguous(), dev)
-
-
+@dataclass
 class _Step:
-    """A launched (not yet processed) decode step."""
-
-    def __init__(self, seqs, key, bk, parity, K, tok_dev, out_host, event):
-        self.seqs, self.key, self.bk, self.parity, self.K = seqs, key, bk, parity, K
-        self.tok_dev, self.out_host, self.event = tok_dev, out_host, event
-        self.static = None  # the launch's static sampler inputs (deferred sampler launch)
-        self.first = None   # first-token step after a prefill: (pinned host outputs, groups)
+    """A launched (not yet processed) step: a decode step, or the first tokens after a prefill (no bucket, no key)."""
+    seqs: List[Sequence]
+    batch: SamplerBatch                      # the launch's sampler inputs (deferred sampler launch)
+    rows: int                                # padded row count of the packed sampler outputs
+    key: object = None
+    bk: Optional[_GraphBucket] = None
+    parity: int = 0
+    tok_dev: Optional[torch.Tensor] = None   # int32 [rows]: the sampled tokens, still on the device
+    out_host: Optional[torch.Tensor] = None
+    event: Optional[torch.cuda.Event] = None
+    groups: Tuple[SequenceGroup, ...] = ()   # their timer.token() fires when the step is processed
 
 
 @dataclass
@@ -389,7 +317,8 @@ class LLMEngine:
         # first tokens after a prefill are sampled asynchronously and processed by the next decode step
         self.async_first_tokens = True
         self._step_no = 0
-        self._comp_cache: Tuple[object, Optional[dict]] = (None, None)
+        self._comp_cache: Tuple[object, Optional[tuple]] = (None, None)  # (composition key, _static_inputs)
+        self._first_host: Optional[torch.Tensor] = None  # grow-only pinned outputs of a first-token step
         self.waiting: Deque[SequenceGroup] = deque()
         self.running: List[Sequence] = []
         self.lock = threading.Lock()
@@ -754,8 +683,7 @@ class LLMEngine:
                 self._cascade_plan(dec, tiles)
                 dec_in["tiles"] = _h2d(tiles, torch.int32, dev)
             else:
-                splits = min(max(1, min(16, -(-1024 // (B * self.cfg.kv_heads)))), max(1, self.width // 4))
-                dec_in["splits"] = splits if self.decode_splits is None else int(self.decode_splits)
+                dec_in["splits"] = self._splits(B)
         cu, k_lens, tables, last_rows = [0], [], [], []
         for g, a, e in items:
             p = g.prompt_ids
@@ -952,22 +880,23 @@ class LLMEngine:
             s.constraint_state = p.constraint.start()
 
     # ------------------------------------------------------------------ decode
+    def _splits(self, B: int) -> int:
+        """Split-K of the plain paged-decode kernel: a launch has >= ~1024 (batch, kv-head, split) workgroups."""
+        if self.decode_splits is not None:
+            return int(self.decode_splits)
+        return min(max(1, min(16, -(-1024 // (B * self.cfg.kv_heads)))), max(1, self.width // 4))
+
     def _bucket(self, B: int) -> _GraphBucket:
         Bb = next((b for b in BUCKETS if b >= B), None)
         if Bb is None:
             raise RuntimeError(f"batch {B} larger than the largest bucket")
         bk = self.buckets.get(Bb)
         if bk is None:
-            # split-K so that a launch has >= ~1024 (batch, kv-head, split) workgroups
-            splits = max(1, min(16, -(-1024 // (Bb * self.cfg.kv_heads))))
-            splits = min(splits, max(1, self.width // 4))
-            if self.decode_splits is not None:
-                splits = int(self.decode_splits)
             max_tiles = 0
             if self.prefix_sharing and Bb >= self.cascade_min_batch:
                 per = ops.cascade_rows_per_tile(self.cfg.heads // self.cfg.kv_heads)
                 max_tiles = cascade_table_size(Bb, per)
-            bk = _GraphBucket(Bb, self.width, splits, max_tiles, self.device)
+            bk = _GraphBucket(Bb, self.width, self._splits(Bb), max_tiles, self.device)
             self.buckets[Bb] = bk
             if hasattr(self.model, "tune_gemms"):
                 # per-shape GEMM backend (ops/gemm_plan.py), measured once per bucket, before any graph
@@ -979,75 +908,34 @@ class LLMEngine:
     def _cascade_plan(self, seqs: List[Sequence], tiles: np.ndarray) -> None:
         """Super-tiles of the cascade decode kernel (see :func:`cascade_tiles`): runs of consecutive
         sequences forked from one prompt share the prompt's full blocks."""
-        runs, i, B = [], 0, len(seqs)
-        while i < B:
-            g = seqs[i].group
-            j = i
-            while j < B and seqs[j].group is g:
-                j += 1
-            runs.append((i, j - i, len(g.prompt_ids) // self.block_size))
-            i = j
+        runs = [(i, n, len(g.prompt_ids) // self.block_size) for i, n, g in _group_runs(seqs)]
         per = ops.cascade_rows_per_tile(self.cfg.heads // self.cfg.kv_heads)
         cascade_tiles(runs, per, tiles)
 
-    def _static_inputs(self, seqs: List[Sequence], key, bk: _GraphBucket) -> dict:
-        """Per-composition inputs (prefix tiles, sampler parameters), rebuilt only when the batch
-        composition changes — in steady-state decoding only positions/slots/offsets move."""
+    def _static_inputs(self, seqs: List[Sequence], key, bk: _GraphBucket) -> Tuple[SamplerBatch, np.ndarray, bool]:
+        """Per-composition inputs (sampler parameters, prefix tiles, whether the cascade kernel runs), rebuilt
+        only when the batch composition changes — in steady-state decoding only positions/slots/offsets move."""
         ck, cached = self._comp_cache
         if ck == key and cached is not None:
             return cached
-        B = bk.B
-        ps = [s.params for s in seqs]
-        n = len(seqs)
-        st = {"tiles": np.zeros((max(1, bk.max_tiles), 3), np.int32),
-              "cascade": bool(bk.max_tiles) and self._cascade_pays(seqs)}
-        if st["cascade"]:
-            self._cascade_plan(seqs, st["tiles"])
-
-        def col(vals, dt, fill=0):
-            a = np.full(B, fill, dtype=dt)
-            a[:n] = vals
-            return a
-
-        st["temperature"] = col([p.temperature for p in ps], np.float32, 1.0)
-        st["top_p"] = col([p.top_p for p in ps], np.float32, 1.0)
-        st["top_k"] = col([p.top_k for p in ps], np.int32)
-        st["min_p"] = col([p.min_p for p in ps], np.float32)
-        st["top_a"] = col([p.top_a for p in ps], np.float32)
-        st["freq_pen"] = col([p.frequency_penalty for p in ps], np.float32)
-        st["pres_pen"] = col([p.presence_penalty for p in ps], np.float32)
-        st["rep_pen"] = col([p.repetition_penalty for p in ps], np.float32, 1.0)
-        st["count_rows"] = col([s.count_row for s in seqs], np.int32, -1)
-        st["bias_rows"] = col([s.group.bias_row for s in seqs], np.int32, -1)
-        st["lora_ids"] = col([s.group.adapter_id for s in seqs], np.int32, -1)  # padding rows: no adapter
-        st["seeds"] = col([s.seed for s in seqs], np.int64)
-        st["K"] = max((p.top_logprobs for p in ps), default=0)
-        st["need_lp"] = any(p.logprobs for p in ps)
-        st["any_pen"] = any(p.uses_penalties for p in ps)
-        st["any_bias"] = any(s.group.bias_row >= 0 for s in seqs)
-        self._comp_cache = (key, st)
-        return st
+        tiles = np.zeros((max(1, bk.max_tiles), 3), np.int32)
+        cascade = bool(bk.max_tiles) and self._cascade_pays(seqs)
+        if cascade:
+            self._cascade_plan(seqs, tiles)
+        self._comp_cache = (key, (SamplerBatch.of(seqs), tiles, cascade))
+        return self._comp_cache[1]
 
     def _cascade_pays(self, seqs: List[Sequence]) -> bool:
         """Whether the cascade kernel beats plain split-K decode for this batch: at least half of its rows
         belong to runs of >= 2 sequences forked from one prompt (candidates of one request).  Batches of
         unrelated sequences (the voters of score requests are separate n = 1 requests) would run the cascade
         kernel as plain decode with one wave walking 16/G whole contexts — few, long-serial workgroups."""
-        shared, i, B = 0, 0, len(seqs)
-        while i < B:
-            g = seqs[i].group
-            j = i
-            while j < B and seqs[j].group is g:
-                j += 1
-            if j - i >= 2 and len(g.prompt_ids) >= self.block_size:
-                shared += j - i
-            i = j
-        return 2 * shared >= B
+        shared = sum(n for _, n, g in _group_runs(seqs) if n >= 2 and len(g.prompt_ids) >= self.block_size)
+        return 2 * shared >= len(seqs)
 
     def _ensure_graph(self, bk: _GraphBucket, cascade: Optional[bool] = None) -> None:
         d = bk.d
         cascade = bool(bk.max_tiles) if cascade is None else cascade
-
         kw = {"lora_ids": d["lora_ids"]} if self.lora is not None else {}
 
         def fwd():
@@ -1076,7 +964,6 @@ class LLMEngine:
                 bk.graph_logits[cascade] = fwd()  # (the bucket's two graphs never run at once)
             bk.pool = g.pool()
             bk.graphs[cascade] = g
-            bk.graph = g
         bk.logits = bk.graph_logits[cascade]
         g.replay()
 
@@ -1210,19 +1097,16 @@ class LLMEngine:
         h = bk.h[parity]
         prepare_decode_into(self.bm, [s.id for s in seqs], bk.width, bk.B, h["block_tables"], h["ctx_lens"],
                             h["slots"], h["positions"])
-        st = self._static_inputs(seqs, key, bk)
+        batch, tiles, cascade = self._static_inputs(seqs, key, bk)
         if bk.host_static_key[parity] != key:
-            for name in ("tiles", "seeds") + _F32_PARAMS + _I32_PARAMS:
-                h[name][...] = st[name]
+            h["tiles"][...] = tiles
+            batch.write(h)
             bk.host_static_key[parity] = key
         prev = self.inflight
-        prev_rows = {}
-        if prev is not None and prev.key != key:
-            prev_rows = {s.id: i for i, s in enumerate(prev.seqs)}
-        offs = h["offsets"]
-        tok_h = h["tokens"]
-        from_prev_dst, from_prev_src = [], []
         same = prev is not None and prev.key == key
+        prev_rows = {s.id: i for i, s in enumerate(prev.seqs)} if prev is not None and not same else {}
+        offs, tok_h = h["offsets"], h["tokens"]
+        from_prev_dst, from_prev_src = [], []
         for i, s in enumerate(seqs):
             offs[i] = s.n_launched
             if not same:
@@ -1239,15 +1123,13 @@ class LLMEngine:
         if same:
             d["tokens"][:B].copy_(prev.tok_dev[:B])
         elif from_prev_dst:
-            dst = torch.tensor(from_prev_dst, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-            src = torch.tensor(from_prev_src, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-            d["tokens"].index_copy_(0, dst, prev.tok_dev.index_select(0, src))
+            d["tokens"].index_copy_(0, _h2d(from_prev_dst, torch.int64, dev),
+                                    prev.tok_dev.index_select(0, _h2d(from_prev_src, torch.int64, dev)))
         if copies:
             self.cache.copy_blocks(_h2d(copies, torch.int32, dev))
-        self._ensure_graph(bk, st["cascade"])
+        self._ensure_graph(bk, cascade)
         self._comm_arm()  # TP: error word of this step's all-reduces -> pinned host memory, read one step later
-        step = _Step(seqs, key, bk, parity, st["K"], None, None, None)
-        step.static = st
+        step = _Step(seqs, batch, bk.B, key, bk, parity)
         self.stats["decode_tokens"] += B
         self.stats["steps"] += 1
         if sample:
@@ -1257,37 +1139,31 @@ class LLMEngine:
     def _launch_sample(self, step: _Step) -> None:
         """Launch the sampler of a launched forward (grammar masks from the sequences' current
         constraint states) and the asynchronous copy of its outputs to pinned host memory."""
-        seqs, bk, parity, st = step.seqs, step.bk, step.parity, step.static
-        B, K, d = len(seqs), step.K, bk.d
-        mask = mask_rows = None
-        cons = [i for i, s in enumerate(seqs) if s.constraint_state is not None]
-        if cons:
-            mask, mask_rows = self._constraint_masks(seqs, cons)
-        outs, out_dev, out_host = bk.outputs(parity, K)
-        ops.sample(bk.logits[:B], temperature=d["temperature"], top_p=d["top_p"], top_k=d["top_k"],
-                   min_p=d["min_p"], top_a=d["top_a"], seeds=d["seeds"], offsets=d["offsets"], num_logprobs=K,
-                   freq_pen=d["freq_pen"] if st["any_pen"] else None,
-                   pres_pen=d["pres_pen"] if st["any_pen"] else None,
-                   rep_pen=d["rep_pen"] if st["any_pen"] else None,
-                   counts=self.counts if st["any_pen"] else None,
-                   count_rows=d["count_rows"] if st["any_pen"] else None,
-                   bias=self.bias if st["any_bias"] else None,
-                   bias_rows=d["bias_rows"] if st["any_bias"] else None,
-                   mask=mask, mask_rows=mask_rows, mask_logprobs=self.constrained_logprobs,
-                   need_logprob=st["need_lp"], out_token=outs[0], out_logprob=outs[1], out_topk_ids=outs[2], out_topk_lp=outs[3])
+        masks = self._constraint_masks(step.seqs)
+        outs, out_dev, out_host = step.bk.outputs(step.parity, step.batch.K)
+        self._sample(step.bk.logits[:len(step.seqs)], step.batch, step.bk.d, masks, outs)
         out_host.copy_(out_dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        step.tok_dev, step.out_host, step.event = outs[0], out_host, ev
+        step.tok_dev, step.out_host, step.event = outs[0], out_host, torch.cuda.Event()
+        step.event.record()
 
-    def _constraint_masks(self, seqs: List[Sequence], cons: List[int]):
-        """(mask table [rows, V/32] int32 on the device, per-sequence row [B] int32).
+    def _sample(self, logits: torch.Tensor, batch: SamplerBatch, d: dict, masks, outs) -> None:
+        """The engine's one ``ops.sample`` call: row parameters from the device views ``d``, into the views ``outs``."""
+        ops.sample(logits, **batch.sample_kwargs(d, self.counts, self.bias), mask=masks[0], mask_rows=masks[1],
+                   mask_logprobs=self.constrained_logprobs, out_token=outs[0], out_logprob=outs[1],
+                   out_topk_ids=outs[2], out_topk_lp=outs[3])
+
+    def _constraint_masks(self, seqs: List[Sequence]):
+        """(mask table [rows, V/32] int32 on the device, per-sequence row [B] int32), or (None, None) for a
+        batch without constrained sequences.
 
         Each constraint maps its FSM state to a cached full-vocabulary token mask + content digest
         (:meth:`TokenConstraint.mask_entry`).  Masks are keyed by that digest: every distinct mask is
         uploaded ONCE into a device-resident table (the voters of a score request, each with its own
         shuffled key enum, still share most states: '{', the property name, quotes, ...), and a step
         uploads only the B row indices."""
+        cons = [i for i, s in enumerate(seqs) if s.constraint_state is not None]
+        if not cons:
+            return None, None
         if self._mask_rows_of is None:
             self._mask_rows_of = {}
             self._mask_table = torch.zeros(64, self.cfg.vocab_size // 32, dtype=torch.int32, device=self.device)
@@ -1301,7 +1177,7 @@ class LLMEngine:
             if r is None:
                 if len(self._mask_rows_of) >= self._mask_limit:  # bounded: start the table over
                     self._mask_rows_of.clear()
-                    return self._constraint_masks(seqs, cons)
+                    return self._constraint_masks(seqs)
                 r = len(self._mask_rows_of)
                 self._mask_rows_of[key] = r
                 new.append((r, ent.words()))
@@ -1322,26 +1198,10 @@ class LLMEngine:
     def _process(self, st: _Step) -> List[TokenEvent]:
         st.event.synchronize()
         self._comm_poll()  # a TP peer that never arrived: CommFailure fails the in-flight groups (EngineService)
-        if st.first is not None:  # first tokens after a prefill (:meth:`_launch_first`)
-            host, groups = st.first
-            lists = [h.tolist() for h in host]
-            events = self._advance(st.seqs, lists[0], lists[1], lists[2] if st.K else None,
-                                   lists[3] if st.K else None)
-            for g in groups:
-                g.timer.token()
-            return events
-        B, K = len(st.seqs), st.K
-        Kb = max(K, 1)
-        Bp = st.bk.B
-        a = st.out_host.numpy()
-        tok_h = a[:B].tolist()
-        lp_h = a[Bp:Bp + B].view(np.float32).tolist()
-        if K:
-            ids_h = a[2 * Bp:2 * Bp + Bp * Kb].reshape(Bp, Kb)[:B, :K].tolist()
-            lps_h = a[2 * Bp + Bp * Kb:2 * Bp + 2 * Bp * Kb].view(np.float32).reshape(Bp, Kb)[:B, :K].tolist()
-        else:
-            ids_h = lps_h = None
-        return self._advance(st.seqs, tok_h, lp_h, ids_h, lps_h)
+        events = self._advance(st.seqs, *unpack_outputs(st.out_host.numpy(), st.rows, len(st.seqs), st.batch.K))
+        for g in st.groups:  # first tokens after a prefill (:meth:`_launch_first`)
+            g.timer.token()
+        return events
 
     def _drain(self) -> List[TokenEvent]:
         st, self.inflight = self.inflight, None
@@ -1438,11 +1298,11 @@ class LLMEngine:
     # ------------------------------------------------------------------ sampling + bookkeeping
     def _sample_and_advance(self, logits: torch.Tensor, seqs: List[Sequence]) -> List[TokenEvent]:
         """Synchronous sampling (first token after prefill)."""
-        tok, lp, tk_ids, tk_lp, K = self._sample_first(logits, seqs)
+        batch, out, _ = self._sample_first(logits, seqs)
         self._comm_arm()
-        host = [t.cpu().tolist() for t in ((tok, lp, tk_ids, tk_lp) if K else (tok, lp))]
-        self._comm_poll()  # the .cpu() reads synchronised the stream: the armed error word is on the host
-        return self._advance(seqs, host[0], host[1], host[2] if K else None, host[3] if K else None)
+        host = out.cpu().numpy()
+        self._comm_poll()  # the .cpu() read synchronised the stream: the armed error word is on the host
+        return self._advance(seqs, *unpack_outputs(host, batch.n, batch.n, batch.K))
 
     def _comm_arm(self) -> None:
         """TP / EP models: queue the readback of the collectives' error word behind the work launched so far.
@@ -1463,56 +1323,32 @@ class LLMEngine:
         to pinned host memory are queued and the result becomes the in-flight step, processed by the
         next decode step after it has launched its own forward — the GPU goes from the prefill
         straight into the next decode step instead of idling while the host forks and advances."""
-        tok, lp, tk_ids, tk_lp, K = self._sample_first(logits, seqs)
-        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in ((tok, lp, tk_ids, tk_lp) if K else
-                                                                               (tok, lp))]
-        for h, t in zip(host, (tok, lp, tk_ids, tk_lp)):
-            h.copy_(t, non_blocking=True)
+        # ONE pinned host buffer, reused: at most one first-token step is unprocessed at any time
+        # (_start_groups launches only with nothing in flight, _mixed_step processes the previous step first)
+        assert self.inflight is None
+        batch, out, tok = self._sample_first(logits, seqs)
+        if self._first_host is None or self._first_host.numel() < out.numel():
+            self._first_host = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
+        host = self._first_host[:out.numel()]
+        host.copy_(out, non_blocking=True)
         self._comm_arm()  # the prefill / mixed forward's collectives: checked by _process before these tokens
         ev = torch.cuda.Event()
         ev.record()
-        st = _Step(seqs, None, None, 0, K, tok, None, ev)
-        st.first = (host, groups)
-        return st
+        return _Step(seqs, batch, batch.n, tok_dev=tok, out_host=host, event=ev, groups=tuple(groups))
 
     def _sample_first(self, logits: torch.Tensor, seqs: List[Sequence]):
-        """Launch the sampler over prefill last-token logits (no host sync); advances n_launched."""
-        B = len(seqs)
-        dev = self.device
-        ps = [s.params for s in seqs]
-        f32 = lambda xs: torch.tensor(xs, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
-        i32 = lambda xs: torch.tensor(xs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        i64 = lambda xs: torch.tensor(xs, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        K = max((p.top_logprobs for p in ps), default=0)
-        any_pen = any(p.uses_penalties for p in ps)
-        any_bias = any(s.group.bias_row >= 0 for s in seqs)
-        cons = [i for i, s in enumerate(seqs) if s.constraint_state is not None]
-        mask = mask_rows = None
-        if cons:
-            mask, mask_rows = self._constraint_masks(seqs, cons)
-        tok, lp, tk_ids, tk_lp = ops.sample(
-            logits,
-            temperature=f32([p.temperature for p in ps]),
-            top_p=f32([p.top_p for p in ps]),
-            top_k=i32([p.top_k for p in ps]),
-            min_p=f32([p.min_p for p in ps]),
-            top_a=f32([p.top_a for p in ps]),
-            seeds=i64([s.seed for s in seqs]),
-            offsets=i64([s.n_launched for s in seqs]),
-            num_logprobs=K,
-            freq_pen=f32([p.frequency_penalty for p in ps]) if any_pen else None,
-            pres_pen=f32([p.presence_penalty for p in ps]) if any_pen else None,
-            rep_pen=f32([p.repetition_penalty for p in ps]) if any_pen else None,
-            counts=self.counts if any_pen else None,
-            count_rows=i32([s.count_row for s in seqs]) if any_pen else None,
-            bias=self.bias if any_bias else None,
-            bias_rows=i32([s.group.bias_row for s in seqs]) if any_bias else None,
-            mask=mask, mask_rows=mask_rows, mask_logprobs=self.constrained_logprobs,
-            need_logprob=any(p.logprobs for p in ps),
-        )
+        """Launch the sampler over prefill last-token logits (no host sync); advances n_launched.  Returns the
+        batch, its packed device outputs (``staging.output_layout`` at rows = len(seqs)) and their token view."""
+        batch = SamplerBatch.of(seqs)
+        masks = self._constraint_masks(seqs)
+        d = batch.upload([s.n_launched for s in seqs], self.device)
+        lay = output_layout(batch.n, batch.K)
+        out = torch.empty(lay.size, dtype=torch.int32, device=self.device)
+        outs = tuple(lay.views(out).values())
+        self._sample(logits, batch, d, masks, outs)
         for s in seqs:
             s.n_launched += 1
-        return tok, lp, tk_ids, tk_lp, K
+        return batch, out, outs[0]
 
     def _advance(self, seqs: List[Sequence], tok_h, lp_h, ids_h, lps_h) -> List[TokenEvent]:
         """Host bookkeeping of one sampled token per sequence: append, grammar advance, stop / length

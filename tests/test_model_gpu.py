@@ -1,5 +1,7 @@
 """Llama decoder + engine on the GPU: kernel-path forward vs an fp32 PyTorch forward, paged decode
 consistency with prefill, prefix-sharing fork/COW, hipGraph replay equivalence."""
+import math
+
 import pytest
 import torch
 
@@ -128,6 +130,75 @@ def test_engine_export_import_prefill_equivalence(tiny, gpu):
     got = [[list(s.tokens) for s in g.seqs] for g in groups]
     assert got == want
     assert b.bm.num_free == 256
+
+
+def _mixed_rows_traces(tiny, use_graphs=True, async_first=True, chunked=0):
+    """One engine, one batch whose rows differ in every sampler column (penalties, bias, top_logprobs, seeds,
+    filters), then the bias and penalty requests again on the same engine (recycled count / bias rows).
+    Returns per request [(top_logprobs asked, per child [(token, logprob, top list)])] of both rounds."""
+    from llm_weighted_consensus_amd.engine.engine import LLMEngine
+    from llm_weighted_consensus_amd.engine.sampling import SamplingParams
+    from llm_weighted_consensus_amd.engine.tokenizer import ByteTokenizer
+
+    tok = ByteTokenizer(tiny.cfg.vocab_size)
+    eng = LLMEngine(tiny, tok, num_blocks=256, max_batch=16, max_model_len=512, use_graphs=use_graphs,
+                    chunked_prefill=chunked)
+    eng.async_first_tokens = async_first
+    eng.collect_events = True
+    sp = lambda **kw: SamplingParams(max_tokens=12, ignore_eos=True, **kw)  # noqa: E731
+    r0 = (tok.encode("rows of one batch that differ"), sp(temperature=0.0), 1)
+    r1 = (tok.encode("a biased row"), sp(temperature=0.0, logit_bias={65: 100}, top_logprobs=2, logprobs=True), 1)
+    r2 = (tok.encode("two penalised children of one prompt"), sp(temperature=0.0, presence_penalty=100), 2)
+    r3 = (tok.encode("three sampled children"), sp(temperature=0.8, top_k=20, top_p=0.9, min_p=0.01, seed=5,
+                                                   top_logprobs=5, logprobs=True), 3)
+
+    def run(reqs):
+        groups = [eng.add_request(p, params, n) for p, params, n in reqs]
+        traces = {}
+        while eng.has_work():
+            for ev in eng.step():
+                traces.setdefault(ev.seq.id, []).append((ev.token_id, ev.logprob, list(ev.top_logprobs)))
+        return [(g.params.top_logprobs, [traces[s.id] for s in g.seqs]) for g in groups]
+
+    first = run([r0, r0, r1, r2, r3])
+    again = run([r1, r2])
+    assert eng.bm.num_free == 256 and len(eng.free_count_rows) == 16 and len(eng.free_bias_rows) == 16
+    return first, again
+
+
+def _check_mixed_rows(first, again, exact):
+    """What every path must give, whatever its logits' last bits; ``exact``: the batch is the same in every step
+    (whole-prompt prefill), so equal requests have equal logprobs too, not only equal tokens."""
+    tokens = lambda req: [[t for t, _, _ in c] for c in req[1]]  # noqa: E731
+    same = (lambda req: req) if exact else tokens  # what two equal requests of one batch must share
+    r0, r0b, r1, r2, r3 = first
+    for k, children in first + again:
+        for trace in children:
+            assert len(trace) == 12
+            for _, lp, top in trace:
+                assert len(top) == k  # each row reports its own request's count, not the batch's
+                assert [v for _, v in top] == sorted((v for _, v in top), reverse=True)
+                assert not k or (math.isfinite(lp) and all(math.isfinite(v) for _, v in top))
+    assert [t for t, _, _ in r1[1][0]] == [65] * 12  # the bias reaches its own row
+    for child in r2[1]:
+        assert len({t for t, _, _ in child}) == 12  # generated tokens are penalised before the greedy pick
+    assert same(r0b) == same(r0)
+    assert len({tuple(t for t, _, _ in c) for c in r3[1]}) > 1  # every child has its own seed
+    # recycled count / bias rows start clean.  Tokens only: the second round's smaller batch runs in another
+    # bucket, whose GEMM backends are timed and chosen on their own, so its logprobs may differ in the last bits
+    assert [tokens(r) for r in again] == [tokens(r1), tokens(r2)]
+
+
+def test_engine_batch_of_rows_that_differ_on_every_sampler_path(tiny, gpu):
+    """Rows that differ in penalties, bias, logprob counts and seeds share one batch: every column reaches its
+    own row on the decode path (graph and eager), on both first-token paths and in mixed chunked-prefill steps,
+    and the three whole-prompt paths give identical (token, logprob, top list) traces."""
+    base = _mixed_rows_traces(tiny)
+    _check_mixed_rows(*base, exact=True)
+    for graphs, async_first in ((True, False), (False, True)):
+        assert _mixed_rows_traces(tiny, use_graphs=graphs, async_first=async_first) == base, (graphs, async_first)
+    # mixed steps: other kernels compute the logits, and prompts complete (rows join the batch) at different steps
+    _check_mixed_rows(*_mixed_rows_traces(tiny, chunked=16), exact=False)
 
 
 @pytest.mark.parametrize("fused", ["ffn2", "all", "0"])
