@@ -82,6 +82,14 @@ void check_v_cache(const at::Tensor& v, const at::Tensor& k, const char* who) {
               who, ": v_cache must be [NB, Hkv, BS/4, D, 4] matching k_cache [NB, Hkv, BS, D]");
 }
 
+// The decode attention kernels are instantiated for head_dim 64 and 128 and carry a KV head's query heads as
+// MFMA rows, so at most 16 of them; the error names the shape that was asked for.
+void check_decode_shape(int D, int Hq, int Hkv, const char* who) {
+  TORCH_CHECK(D == 64 || D == 128, who, ": head_dim ", D, ": decode attention takes 64 or 128");
+  TORCH_CHECK(Hkv > 0 && Hq > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, who, ": ", Hq, " heads / ", Hkv,
+              " kv heads (GQA group ", Hkv > 0 ? Hq / Hkv : 0, "): decode attention takes whole groups up to 16");
+}
+
 #define CHECK_GPU(t) TORCH_CHECK((t).is_cuda(), #t " must be a GPU tensor")
 #define CHECK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 #define CHECK_DTYPE(t, dt) TORCH_CHECK((t).scalar_type() == (dt), #t " has dtype ", (t).scalar_type(), ", expected ", dt)
@@ -318,6 +326,8 @@ void paged_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tens
   TORCH_CHECK(q.stride(-1) == 1, "paged_decode: q rows must be contiguous");
   const int B = (int)out.size(0), Hq = (int)out.size(1), D = (int)out.size(2);
   const int Hkv = (int)k_cache.size(1), BS = (int)k_cache.size(2);
+  check_decode_shape(D, Hq, Hkv, "paged_decode");
+  TORCH_CHECK(k_cache.size(3) == D, "paged_decode: out is [B, Hq, ", D, "] but the cache has head_dim ", k_cache.size(3));
   TORCH_CHECK(q.size(0) == B && q.size(1) >= Hq * D, "paged_decode: q shape");
   check_v_cache(v_cache, k_cache, "paged_decode");
   TORCH_CHECK(block_tables.size(0) == B && ctx_lens.numel() == B, "paged_decode: batch mismatch");
@@ -357,6 +367,8 @@ void paged_decode_cascade(const at::Tensor& q, const at::Tensor& k_cache, const 
   TORCH_CHECK(tiles.dim() == 2 && tiles.size(1) == 3, "paged_decode_cascade: tiles must be [T, 3]");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1, "paged_decode_cascade: q must be [B, >=Hq*D] rows");
   const int B = (int)q.size(0), D = (int)k_cache.size(3), Hkv = (int)k_cache.size(1), BS = (int)k_cache.size(2);
+  check_decode_shape(D, (int)Hq, Hkv, "paged_decode_cascade");
+  TORCH_CHECK(q.size(1) >= Hq * D, "paged_decode_cascade: q rows shorter than Hq * D");
   TORCH_CHECK(block_tables.size(0) >= B && ctx_lens.numel() >= B, "paged_decode_cascade: batch tables too short");
   void* outp = nullptr;
   void* o8 = nullptr;
@@ -366,7 +378,8 @@ void paged_decode_cascade(const at::Tensor& q, const at::Tensor& k_cache, const 
     CHECK_GPU(*out8); CHECK_CONTIG(*out8); CHECK_GPU(*mx); CHECK_CONTIG(*mx); CHECK_DTYPE(*mx, at::kByte);
     TORCH_CHECK(out8->scalar_type() == at::kFloat8_e4m3fn && out8->numel() >= (int64_t)B * Hq * D,
                 "paged_decode_cascade: out8 must be e4m3 [B, Hq * D]");
-    TORCH_CHECK(mx->dim() == 3 && mx->size(0) == Hq && mx->size(1) >= B && mx->size(2) == 4 && D == 128,
+    TORCH_CHECK(D == 128, "paged_decode_cascade: head_dim ", D, ": the MX output takes head_dim 128 only");
+    TORCH_CHECK(mx->dim() == 3 && mx->size(0) == Hq && mx->size(1) >= B && mx->size(2) == 4,
                 "paged_decode_cascade: mx must be [Hq, B, 4] (head_dim 128)");
     o8 = out8->data_ptr();
     mxp = mx->data_ptr();

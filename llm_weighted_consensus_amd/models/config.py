@@ -49,6 +49,22 @@ class DecoderConfig:
         return self.layers * (attn + mlp + 2 * d) + emb + d
 
 
+def check_decoder(cfg: DecoderConfig) -> None:
+    """Refuse, by name, a decoder shape the kernels do not serve (models call this before building anything).
+
+    Decode attention takes head_dim 64 or 128 and any whole GQA group up to 16.  The fused Qwen attention-block
+    pass (bias / per-head QK RMSNorm, csrc/kernels/qknorm.hip) exists for head_dim 128 only."""
+    if cfg.head_dim not in (64, 128):
+        raise ValueError(f"{cfg.name}: head_dim {cfg.head_dim}: decode attention takes 64 or 128")
+    if cfg.kv_heads <= 0 or cfg.heads % cfg.kv_heads or cfg.heads // cfg.kv_heads > 16:
+        raise ValueError(f"{cfg.name}: {cfg.heads} heads / {cfg.kv_heads} kv heads: decode attention takes whole "
+                         "GQA groups up to 16")
+    if cfg.head_dim != 128 and (cfg.qkv_bias or cfg.qk_norm):
+        what = " and ".join(n for n, on in (("qkv_bias", cfg.qkv_bias), ("qk_norm", cfg.qk_norm)) if on)
+        raise ValueError(f"{cfg.name}: {what} at head_dim {cfg.head_dim}: the Qwen attention block is served at "
+                         "head_dim 128 only")
+
+
 @dataclass(frozen=True)
 class EncoderConfig:
     name: str
@@ -78,7 +94,20 @@ DECODERS = {
     # e5-mistral-7b-instruct: Mistral-7B decoder used as an embedder (last-token pooling, 4096-d)
     "e5-mistral-7b": DecoderConfig("e5-mistral-7b", 32000, 4096, 32, 32, 8, 128, 14336, rope_theta=10000.0,
                                    rms_eps=1e-5, max_position=32768),
+    # Llama-3.2 text models (tied embeddings; 1B: head_dim 64, 3B: a GQA group of 3).  These shapes, and the
+    # Qwen ones added with them below, are written from memory of the public config.json files and could not be
+    # checked against them when they were added; a checkpoint whose tensors disagree is refused at load.
+    "llama-3.2-1b": DecoderConfig("llama-3.2-1b", 128256, 2048, 16, 32, 8, 64, 8192, rope_theta=500000.0,
+                                  rms_eps=1e-5, max_position=131072, rope_scaling=(32.0, 1.0, 4.0, 8192),
+                                  tie_embeddings=True, bos_token_id=128000, eos_token_id=128001),
+    "llama-3.2-3b": DecoderConfig("llama-3.2-3b", 128256, 3072, 28, 24, 8, 128, 8192, rope_theta=500000.0,
+                                  rms_eps=1e-5, max_position=131072, rope_scaling=(32.0, 1.0, 4.0, 8192),
+                                  tie_embeddings=True, bos_token_id=128000, eos_token_id=128001),
     # tests / smoke: same code paths, tiny sizes
+    "llama-hd64-tiny": DecoderConfig("llama-hd64-tiny", 4096, 512, 2, 8, 2, 64, 1024, rope_theta=500000.0,
+                                     max_position=2048, bos_token_id=1, eos_token_id=2),
+    "llama-g3-tiny": DecoderConfig("llama-g3-tiny", 4096, 512, 2, 6, 2, 128, 1024, rope_theta=500000.0,
+                                   max_position=2048, bos_token_id=1, eos_token_id=2),
     "llama-tiny": DecoderConfig("llama-tiny", 4096, 512, 2, 8, 2, 128, 1024, rope_theta=500000.0, max_position=2048,
                                 bos_token_id=1, eos_token_id=2),
     "mixtral-tiny": DecoderConfig("mixtral-tiny", 4096, 512, 2, 8, 2, 128, 512, rope_theta=1e6, max_position=2048,
@@ -92,14 +121,20 @@ def _qwen(name: str, vocab: int, hidden: int, layers: int, heads: int, kv_heads:
                          max_position=32768, tie_embeddings=tie, bos_token_id=None, eos_token_id=151645, **flags)
 
 
-# Qwen3 (per-head q/k RMSNorm) and Qwen2.5 (q|k|v bias): the sizes whose GQA group divides 16 and whose
-# head_dim is 128, which is what the decode attention kernels take.  Qwen2.5-7B/14B/32B and Qwen3-14B (groups
-# of 7 and 5) and the 0.5B / 1.5B models (head_dim 64 or a group of 6) are not registered.
+# Qwen3 (per-head q/k RMSNorm) and Qwen2.5 (q|k|v bias) at head_dim 128, with any GQA group up to 16 (the decode
+# attention kernels take groups that do not divide 16: 5, 6 and 7 here).  Qwen2.5-0.5B (head_dim 64 with a
+# bias) is not registered: the fused bias / QK-norm pass exists for head_dim 128 only (check_decoder).  The
+# 1.5b / 7b / 14b / 32b and qwen3-14b rows are from memory of the public configs (see the Llama-3.2 note above).
 DECODERS.update({
     "qwen3-0.6b": _qwen("qwen3-0.6b", 151936, 1024, 28, 16, 8, 3072, True, qk_norm=True),
     "qwen3-4b": _qwen("qwen3-4b", 151936, 2560, 36, 32, 8, 9728, True, qk_norm=True),
     "qwen3-8b": _qwen("qwen3-8b", 151936, 4096, 36, 32, 8, 12288, False, qk_norm=True),
     "qwen3-32b": _qwen("qwen3-32b", 151936, 5120, 64, 64, 8, 25600, False, qk_norm=True),
+    "qwen3-14b": _qwen("qwen3-14b", 151936, 5120, 40, 40, 8, 17408, False, qk_norm=True),
+    "qwen2.5-1.5b": _qwen("qwen2.5-1.5b", 151936, 1536, 28, 12, 2, 8960, True, qkv_bias=True),
+    "qwen2.5-7b": _qwen("qwen2.5-7b", 152064, 3584, 28, 28, 4, 18944, False, qkv_bias=True),
+    "qwen2.5-14b": _qwen("qwen2.5-14b", 152064, 5120, 48, 40, 8, 13824, False, qkv_bias=True),
+    "qwen2.5-32b": _qwen("qwen2.5-32b", 152064, 5120, 64, 40, 8, 27648, False, qkv_bias=True),
     "qwen2.5-3b": _qwen("qwen2.5-3b", 151936, 2048, 36, 16, 2, 11008, True, qkv_bias=True),
     "qwen2.5-72b": _qwen("qwen2.5-72b", 152064, 8192, 80, 64, 8, 29568, False, qkv_bias=True),
     # tests: the two attention-block variants at llama-tiny sizes
@@ -107,6 +142,11 @@ DECODERS.update({
                           eos_token_id=2),
     "qwen2-tiny": replace(_qwen("qwen2-tiny", 4096, 512, 2, 8, 2, 1024, False, qkv_bias=True), max_position=2048,
                           eos_token_id=2),
+    # ... and at GQA groups that do not divide 16 (heads * head_dim != hidden, as in Qwen3)
+    "qwen2-g7-tiny": replace(_qwen("qwen2-g7-tiny", 4096, 512, 2, 14, 2, 1024, False, qkv_bias=True),
+                             max_position=2048, eos_token_id=2),
+    "qwen3-g5-tiny": replace(_qwen("qwen3-g5-tiny", 4096, 512, 2, 10, 2, 1024, True, qk_norm=True),
+                             max_position=2048, eos_token_id=2),
 })
 
 ENCODERS = {

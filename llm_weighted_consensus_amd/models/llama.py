@@ -41,7 +41,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops import blas_tuning, gemm_plan
 from . import step_plan
-from .config import DecoderConfig
+from .config import DecoderConfig, check_decoder
 from .step_plan import ChainPlan
 
 
@@ -115,6 +115,7 @@ class LlamaModel:
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
                  fold_norms: bool = True, lora=None):
+        check_decoder(cfg)  # shapes the kernels do not serve are refused here, by arch name
         if cfg.num_experts and type(self) is LlamaModel:
             raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
         # LoRA adapters (``lora``: a list of models/lora.py Adapters, laid out here once for this model's weights

@@ -163,6 +163,16 @@ def kv_block_copy(cache: torch.Tensor, pairs: torch.Tensor) -> None:
 # attention
 
 
+def _check_decode_shape(who: str, D: int, Hq: int, Hkv: int) -> None:
+    """The decode attention kernels exist for head_dim 64 and 128 and carry one KV head's query heads as MFMA
+    rows (at most 16); anything else is refused here, with the shape named, before a launch."""
+    if D not in (64, 128):
+        raise ValueError(f"{who}: head_dim {D}: decode attention takes 64 or 128")
+    if Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or Hq // Hkv > 16:
+        raise ValueError(f"{who}: {Hq} heads / {Hkv} kv heads (GQA group {Hq / max(Hkv, 1):g}): decode attention "
+                         "takes whole groups up to 16")
+
+
 def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
                  ctx_lens: torch.Tensor, Hq: int, scale: float, num_splits: int = 1,
                  out: Optional[torch.Tensor] = None, part_o: Optional[torch.Tensor] = None,
@@ -170,9 +180,11 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
                  rope: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """One-token paged GQA split-K decode attention (K3).  q: [B, >=Hq*D] (row stride allowed).  The
     engine's large batches of forked candidates use :func:`paged_decode_cascade` instead.  ``rope`` =
-    (cos, sin, positions [B] int32): q arrives un-rotated and is rotated at load."""
+    (cos, sin, positions [B] int32): q arrives un-rotated and is rotated at load.  head_dim (the caches' last
+    K dimension) is 64 or 128 and the GQA group any whole number up to 16; other shapes raise ``ValueError``."""
     B = q.shape[0]
     D = k_cache.shape[-1]
+    _check_decode_shape("paged_decode", D, int(Hq), k_cache.shape[1])
     if out is None:
         out = torch.empty(B, Hq, D, dtype=q.dtype, device=q.device)
     if num_splits > 1 and (part_o is None or part_lse is None):
@@ -191,7 +203,9 @@ def set_decode_wave_min_items(n: int) -> int:
 
 
 def cascade_rows_per_tile(G: int) -> int:
-    """Sequences per cascade super-tile (8 waves x 16/G sequences)."""
+    """Sequences per cascade super-tile: 8 waves x floor(16 / G) whole sequences each, for any GQA group
+    G <= 16 (64 at G = 2, 32 at 4, 16 at 8; 40 at G = 3, 24 at 5, 16 at 6 and 7, whose waves leave 16 mod G
+    MFMA rows idle)."""
     return int(kernels().cascade_rows_per_tile(int(G)))
 
 
@@ -222,6 +236,9 @@ def paged_decode_cascade(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     separate quantisation pass."""
     B = q.shape[0]
     D = k_cache.shape[-1]
+    _check_decode_shape("paged_decode_cascade", D, int(Hq), k_cache.shape[1])
+    if mx and D != 128:
+        raise ValueError(f"paged_decode_cascade: head_dim {D}: the MX output takes head_dim 128 only")
     rc, rs, rp = rope if rope is not None else (None, None, None)
     if mx:
         q8 = torch.empty(B, Hq * D, dtype=torch.float8_e4m3fn, device=q.device)

@@ -351,6 +351,52 @@ def attention_prefix(dev):
               f"no-sharing full ctx {t_f:7.1f} us", flush=True)
 
 
+def decode_shapes(dev):
+    """One cascade decode attention layer at head_dim 64 and 128 (Hkv 8, G 4): B = 4096 sequences in 64 groups of
+    64 candidates, a 128-token shared prompt and 64 generated tokens each.  The two shapes alternate inside one
+    run (5 rounds of 50 launches each, median); bytes are what the algorithm needs: the prompt's K and V once
+    per (super-tile, KV head), every sequence's own K and V, q in and the output out."""
+    import numpy as np
+
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.engine.engine import cascade_table_size, cascade_tiles
+
+    Hkv, G, BS, R, N, P, gen = 8, 4, 16, 64, 64, 8, 64
+    Hq, B, sblk = Hkv * G, R * N, gen // BS
+    per_t = ops.cascade_rows_per_tile(G)
+    ct = np.zeros((cascade_table_size(B, per_t), 3), dtype=np.int32)
+    nt = cascade_tiles([(r * N, N, P) for r in range(R)], per_t, ct)
+    ct = torch.from_numpy(ct).to(dev)
+    bt = torch.zeros(B, P + sblk, dtype=torch.int32)
+    for r in range(R):
+        bt[r * N:(r + 1) * N, :P] = torch.arange(r * P, (r + 1) * P, dtype=torch.int32)
+    bt[:, P:] = (R * P + torch.arange(B * sblk, dtype=torch.int32)).view(B, sblk)
+    bt = bt.to(dev)
+    ctx = torch.full((B,), P * BS + gen, device=dev, dtype=torch.int32)
+    runs, nbytes = {}, {}
+    for D in (64, 128):
+        NB = R * P + B * sblk + 8
+        kc = torch.randn(NB, Hkv, BS, D, device=dev).to(torch.bfloat16)
+        vc = torch.randn(NB, Hkv, BS // 4, D, 4, device=dev).to(torch.bfloat16)
+        q = torch.randn(B, (Hq + 2 * Hkv) * D, device=dev).to(torch.bfloat16)
+        out = torch.empty(B, Hq, D, device=dev, dtype=torch.bfloat16)
+        runs[D] = (lambda q=q, kc=kc, vc=vc, out=out, D=D:
+                   ops.paged_decode_cascade(q, kc, vc, bt, ctx, ct, Hq, 1 / math.sqrt(D), out=out))
+        nbytes[D] = 2 * 2 * D * Hkv * (nt * P * BS + B * gen) + 2 * 2 * B * Hq * D
+        got = runs[D]().float()
+        ref_o = ops.paged_decode(q, kc, vc, bt, ctx, Hq, 1 / math.sqrt(D)).float()
+        print(f"decode-shapes D={D}: max|cascade - plain| {(got - ref_o).abs().max().item():.3g}", flush=True)
+    times = {D: [] for D in runs}
+    for _ in range(5):
+        for D in runs:
+            times[D].append(timeit(runs[D]))
+    for D in runs:
+        t = sorted(times[D])
+        print(f"decode-shapes cascade Hkv={Hkv} G={G} D={D} B={B} prompt={P * BS} gen={gen} ({nt} tiles): "
+              f"median {t[2]:7.1f} us (min {t[0]:.1f}, max {t[4]:.1f}), {nbytes[D] / 1e6:.1f} MB needed, "
+              f"{nbytes[D] / t[2] / 1e6:.2f} TB/s", flush=True)
+
+
 def prefill_attn(dev):
     """Chunk-prefill attention: queries = the last q rows of a k-key range, keys contiguous (cached-prefix
     path, after kv_gather) vs paged (block tables, the mixed chunked-prefill path); + the gather itself."""
@@ -990,6 +1036,8 @@ def main():
         prefill_attn(dev)
     if "prefix" in a.what:
         attention_prefix(dev)
+    if "decode_shapes" in a.what:
+        decode_shapes(dev)
     if "sample" in a.what:
         sampler(dev)
     if "moe" in a.what:
