@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(kSampT) sample_kernel(SampleParams p) {
   __shared__ int sredi[32];
   __shared__ float s_cval[kCollect];
   __shared__ int s_cidx[kCollect];
-  __shared__ int s_ccount;
+  __shared__ int s_ccount[2];  // collected: [0] candidates, [1] ties at the threshold of an exact search
   __shared__ float s_scan[kSampT / 64];
   __shared__ uint32_t s_tkey[kSampT];
   __shared__ uint32_t s_lb, s_fkey;
@@ -217,7 +217,13 @@ OPAQUE_ROW(row);
     // then collected in one pass.  Only if they overflow the collection buffer does the exact 16-round
     // search over the whole row run (starting from lb).  Masked (-inf, key 0x7f) entries are never
     // candidates: a row with < K finite values returns fewer (rest: id -1).
-    if (t == 0) s_ccount = 0;
+    // After the exact search any number of elements may still TIE at the K-th key, and appended in arrival
+    // order they would fill the buffer before an element strictly above the threshold (the row maximum
+    // included) arrives.  So the second collection counts the two kinds apart: the elements above the
+    // threshold, at most K - 1, take the slots from 0 upwards, the ties the slots from kCollect - 1 downwards
+    // as far as slot K - 1.  Up to kCollect - (K - 1) ties are all held and come out in index order; of more,
+    // which of the tied tokens are held is a matter of arrival (their logprob is the same).
+    if (t == 0) s_ccount[0] = s_ccount[1] = 0;
     s_tkey[t] = my_maxkey;
     __syncthreads();
     if (t < 64) {
@@ -254,7 +260,7 @@ OPAQUE_ROW(row);
             hi = mid - 1;
         }
         __syncthreads();
-        if (t == 0) s_ccount = 0;
+        if (t == 0) s_ccount[0] = 0;
         __syncthreads();
       }
       // candidates are sparse (a few dozen of 128k): one float compare per element and a wave-uniform
@@ -262,6 +268,7 @@ OPAQUE_ROW(row);
       // key test and the LDS append (key2f(lo) is the smallest value with key >= lo, so the float test
       // passes a superset: -0 next to +0)
       const float thr = key2f(lo);
+      const uint32_t tiekey = attempt ? lo : 0xffffffffu;  // no key matches on the first pass
 OPAQUE_ROW(row);
 #pragma unroll
       for (int j = 0; j < SLOTS; ++j)
@@ -271,9 +278,12 @@ OPAQUE_ROW(row);
           const bool h = v >= thr;
           if (__builtin_amdgcn_ballot_w64(h)) {
             const int idx = (j * kSampT + t) * 8 + e;
-            if (h && f2key(v) >= lo) {  // padding past V holds -inf (key 0x7f < lo): never collected
-              const int slot = atomicAdd(&s_ccount, 1);
-              if (slot < kCollect) {
+            const uint32_t kv = f2key(v);
+            if (h && kv >= lo) {  // padding past V holds -inf (key 0x7f < lo): never collected
+              const int tie = kv == tiekey;
+              const int c = atomicAdd(&s_ccount[tie], 1);
+              const int slot = tie * (kCollect - 1) + (1 - 2 * tie) * c;  // c upwards, or kCollect - 1 - c
+              if ((unsigned)slot < (unsigned)kCollect && slot >= tie * (K - 1)) {
                 s_cval[slot] = v;
                 s_cidx[slot] = idx;
               }
@@ -281,7 +291,7 @@ OPAQUE_ROW(row);
           }
         }
       __syncthreads();
-      if (s_ccount <= kCollect) break;  // block-uniform
+      if (s_ccount[0] <= kCollect) break;  // block-uniform
     }
   }
 
@@ -682,16 +692,23 @@ OPAQUE_ROW(row);
     token = found;
   }
   if (K > 0 && t < 64) {  // one wave: rank-sort the collected top-K candidates (value desc, index asc)
-    const int n = min(s_ccount, kCollect);
+    // candidates: slots [0, n0) and, after an exact search (then n0 <= K - 1), the ties at the threshold in
+    // [tbeg, kCollect), tbeg >= K - 1
+    const int n0 = min(s_ccount[0], kCollect), n1 = min(s_ccount[1], kCollect - (K - 1));
+    const int n = n0 + n1, tbeg = kCollect - n1;
     for (int r = n + t; r < K; r += 64) {  // fewer finite values than K: empty slots
       p.out_topk_ids[(size_t)b * K + r] = -1;
       p.out_topk_lp[(size_t)b * K + r] = -INFINITY;
     }
-    if (t < n) {
+    if (t < n0 || t >= tbeg) {
       const float v = s_cval[t];
       const int ix = s_cidx[t];
       int rank = 0;
-      for (int u = 0; u < n; ++u) {
+      for (int u = 0; u < n0; ++u) {
+        const float w = s_cval[u];
+        rank += (w > v) || (w == v && s_cidx[u] < ix);
+      }
+      for (int u = tbeg; u < kCollect; ++u) {
         const float w = s_cval[u];
         rank += (w > v) || (w == v && s_cidx[u] < ix);
       }

@@ -435,6 +435,13 @@ def test_prefill_attention_paged(gpu, Hq, Hkv):
 
 
 def _sample(logits, dev, n=None, **kw):
+    """ops.sample with scalar per-row parameters.  The sampler tests below use random rows and 4096-draw
+    histograms at V = 4096 and 32000 (the SLOTS=4 instance) and 128256 (SLOTS=16).  Structured inputs — one-hot
+    rows on every edge position of the row, kept sets known exactly, pairs that share a dword or a thread, the
+    top-logprob overflow and tie paths, processing at full vocabulary and the call contract — are in
+    tests/test_sampler_probes_gpu.py (inputs and float64 references: tests/sampler_probes.py; shown to reject
+    wrong references on the CPU: tests/test_sampler_probes.py), at V = 32000 (SLOTS=4), 65504 (SLOTS=8), 128256
+    (SLOTS=16) and the Qwen vocabularies 151936 and 152064 (SLOTS=20)."""
     from llm_weighted_consensus_amd import ops
 
     B = logits.shape[0]
