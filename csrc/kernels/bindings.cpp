@@ -32,6 +32,8 @@ int lwc_gemm4w(const void*, const void*, void*, const void*, int, int, int, int,
                float, int, int, int, int, float*, int*, hipStream_t);
 int lwc_rms_rowsumsq(const void*, float*, int, int, hipStream_t);
 int lwc_skinny_gemm(const void*, const void*, void*, const void*, int, int, int, int, int, int, hipStream_t);
+int lwc_mxfp4_dequant(const void*, const void*, void*, long long, long long, hipStream_t);
+int lwc_skinny_mxfp4(const void*, const void*, const void*, void*, int, int, int, int, int, int, hipStream_t);
 int lwc_lora_shrink(const void*, const void*, const int*, void*, int, int, int, int, int, hipStream_t);
 int lwc_lora_expand_add(void*, const void*, const void*, const int*, int, int, int, int, int, hipStream_t);
 int lwc_gemm8g_fp8(const void*, const void*, void*, const int*, const int*, const float*, const float*, int, int, int,
@@ -546,6 +548,47 @@ void skinny_gemm(const at::Tensor& A, const at::Tensor& W, at::Tensor& C, const 
            "skinny_gemm");
 }
 
+// MXFP4 weight (mxfp4.hip): q [N, K / 2] uint8 (two e2m1 codes per byte), s [N, K / 32] uint8 (e8m0)
+void mxfp4_check_weight(const at::Tensor& q, const at::Tensor& s, const char* who) {
+  CHECK_GPU(q); CHECK_DTYPE(q, at::kByte); CHECK_CONTIG(q);
+  CHECK_GPU(s); CHECK_DTYPE(s, at::kByte); CHECK_CONTIG(s);
+  TORCH_CHECK(q.dim() == 2 && s.dim() == 2 && s.size(0) == q.size(0) && q.size(1) == 16 * s.size(1), who,
+              ": q must be [N, K / 2] and s [N, K / 32] with K % 32 == 0");
+}
+
+// out [N, K] bf16 (caller-owned) = the dequantised weight, exact
+void mxfp4_dequant(const at::Tensor& q, const at::Tensor& s, at::Tensor& out) {
+  mxfp4_check_weight(q, s, "mxfp4_dequant");
+  CHECK_BF16(out); CHECK_CONTIG(out);
+  const int64_t N = q.size(0), K = 2 * q.size(1);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N && out.size(1) == K, "mxfp4_dequant: out must be [N, K] = [", N, ", ",
+              K, "]");
+  CHECK_RC(lwc_mxfp4_dequant(q.data_ptr(), s.data_ptr(), out.data_ptr(), (long long)N, (long long)K, cur_stream()),
+           "mxfp4_dequant");
+}
+
+// skinny GEMM over an MXFP4 weight (M <= 64): C = A . W^T (epi 0) or the SwiGLU of a 32-row gate/up interleaved W
+// (epi 2, C [M, N / 2])
+void skinny_mxfp4(const at::Tensor& A, const at::Tensor& q, const at::Tensor& s, at::Tensor& C, int64_t epi) {
+  TORCH_CHECK(epi == 0 || epi == 2, "skinny_mxfp4: epi 0 (plain) or 2 (SwiGLU)");
+  mxfp4_check_weight(q, s, "skinny_mxfp4");
+  CHECK_BF16(A); CHECK_BF16(C);
+  TORCH_CHECK(A.dim() == 2 && A.stride(1) == 1 && C.dim() == 2 && C.stride(1) == 1, "skinny_mxfp4: 2-D row-major A / C");
+  const int64_t M = A.size(0), K = A.size(1), N = q.size(0);
+  const int64_t NC = epi == 2 ? N / 2 : N;
+  TORCH_CHECK(2 * q.size(1) == K && C.size(0) == M && C.size(1) == NC, "skinny_mxfp4: shape mismatch (A [", M, ", ", K,
+              "], W [", N, ", ", 2 * q.size(1), "], C [", C.size(0), ", ", C.size(1), "])");
+  TORCH_CHECK(M <= 64 && K % 128 == 0 && N % (epi == 2 ? 64 : 16) == 0,
+              "skinny_mxfp4: needs M <= 64, K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0); got M = ", M, ", K = ", K,
+              ", N = ", N);
+  TORCH_CHECK(A.stride(0) % 4 == 0 && C.stride(0) % 4 == 0 && A.stride(0) >= K && C.stride(0) >= NC &&
+                  (uintptr_t)A.data_ptr() % 8 == 0 && (uintptr_t)C.data_ptr() % 8 == 0,
+              "skinny_mxfp4: rows of A / C must be 8-byte aligned and not overlap");
+  CHECK_RC(lwc_skinny_mxfp4(A.data_ptr(), q.data_ptr(), s.data_ptr(), C.data_ptr(), (int)M, (int)N, (int)K,
+                            (int)A.stride(0), (int)C.stride(0), (int)epi, cur_stream()),
+           "skinny_mxfp4");
+}
+
 // batched LoRA (lora.hip): T[m] = X[m] . A[ids[m]]^T, then Y[m] += T[m] . B[ids[m]]^T; ids outside
 // [0, n_adapters) (-1) mean no adapter: the row of T is not written, the row of Y not touched
 void lora_check_ids(const at::Tensor& ids, int64_t M, const char* who) {
@@ -1047,6 +1090,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm8p", &gemm8p);
   m.def("gemm4w", &gemm4w);
   m.def("skinny_gemm", &skinny_gemm);
+  m.def("mxfp4_dequant", &mxfp4_dequant);
+  m.def("skinny_mxfp4", &skinny_mxfp4);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand_add", &lora_expand_add);
   m.def("rms_rowsumsq", &rms_rowsumsq);

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import blas_tuning, gemm_plan
+from ..ops.mxfp4 import Mxfp4Weight
 from . import step_plan
 from .config import DecoderConfig, check_decoder
 from .step_plan import ChainPlan
@@ -114,8 +115,22 @@ class _NullCache:
 class LlamaModel:
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
-                 fold_norms: bool = True, lora=None):
+                 fold_norms: bool = True, lora=None, mxfp4: bool = False):
         check_decoder(cfg)  # shapes the kernels do not serve are refused here, by arch name
+        # MXFP4 weight-only projections (ops/mxfp4.py): qkv / o / gate|up / down as 4-bit codes with one e8m0
+        # scale per 32, bf16 activations; the dense single-GPU decoder only.  On a CPU device the model holds the
+        # dequantised bf16 weights (the same function, through F.linear)
+        if mxfp4:
+            if cfg.num_experts:
+                raise ValueError(f"mxfp4 weights are not supported on MoE decoders ({cfg.name})")
+            if type(self) is not LlamaModel:
+                raise ValueError("mxfp4 weights do not combine with tensor parallelism (tp > 1)")
+            if fp8_dense:
+                raise ValueError("mxfp4 weights do not combine with fp8 weights")
+            if lora is not None:
+                raise ValueError("mxfp4 weights do not combine with LoRA adapters")
+        self.mxfp4 = bool(mxfp4)
+        self.mx_scratch: Optional[torch.Tensor] = None  # bf16, the largest projection (ops.linear_mxfp4)
         if cfg.num_experts and type(self) is LlamaModel:
             raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
         # LoRA adapters (``lora``: a list of models/lora.py Adapters, laid out here once for this model's weights
@@ -137,6 +152,11 @@ class LlamaModel:
             self._random_init(seed)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
         self.g8_ws = None
+        if self.mxfp4 and self.device.type == "cuda":
+            # one dequantisation buffer for every projection past 64 rows, allocated here: never inside a capture
+            n = max(math.prod(w.shape) for L in self.layers for w in (L.wqkv, L.wo, L.w_gate_up, L.w_down))
+            self.mx_scratch = torch.empty(n, dtype=torch.bfloat16, device=self.device)
+            torch.cuda.empty_cache()
         # fp8 configurations (BASELINE config 5: the e5-mistral embedder): the qkv / o / gate|up / down
         # projections in e4m3 with per-channel scales, activations quantised per row; lm_head stays bf16
         self.fp8_dense = bool(fp8_dense) and self.device.type == "cuda"
@@ -176,7 +196,8 @@ class LlamaModel:
             self.lora = lora
         self.pinned: dict = {}  # decode batch M -> a fixed step plan (pin_step_plan): nothing is timed at M
         # ``fold_norms=False``: models that never decode through lm_head (the decoder-as-embedder) skip it
-        if (fold_norms and self.device.type == "cuda" and not self.fp8_dense and type(self) is LlamaModel
+        if (fold_norms and self.device.type == "cuda" and not self.fp8_dense and not self.mxfp4
+                and type(self) is LlamaModel
                 and os.environ.get("LWC_NORM_FOLD", "1") != "0" and isinstance(self.layers[0], LayerWeights)):
             self._fold_norms()
 
@@ -237,12 +258,41 @@ class LlamaModel:
                     return (1.0 + 0.3 * torch.randn(cfg.head_dim, generator=g, device=dev, dtype=torch.float32)).to(dt)
 
                 self.layers[-1].q_norm, self.layers[-1].k_norm = norm_w(), norm_w()
+            if self.mxfp4:
+                self._quantise_layer(self.layers[-1])
         self.final_norm = torch.ones(d, device=dev, dtype=dt)
         self.lm_head = self.embed if cfg.tie_embeddings else rnd(cfg.vocab_size, d)
 
+    def _quantise_layer(self, L: LayerWeights) -> None:
+        """``mxfp4=True``: the layer's four projections become ops.Mxfp4Weight (a bf16 tensor is quantised and
+        freed; a pre-quantised one is taken as it is), gate|up after its 32-row SwiGLU interleave — a row
+        permutation, so it applies to the codes and scales directly.  Called as each layer is built, so at most
+        one layer's bf16 projections are alive.  On a CPU device the layer holds the dequantised bf16 tensors in
+        the plain row order."""
+        gpu = self.device.type == "cuda"
+
+        def one(w, interleave=False):
+            if isinstance(w, Mxfp4Weight):
+                if interleave:
+                    w = Mxfp4Weight.from_packed(ops.swiglu_interleave(w.q), ops.swiglu_interleave(w.s))
+            else:
+                w = Mxfp4Weight(ops.swiglu_interleave(w) if interleave else w)
+            return w if gpu else w.dequant()
+
+        il = gpu and L.gu_block == 0 and L.w_gate_up.shape[0] % 64 == 0
+        L.wqkv, L.wo, L.w_down = one(L.wqkv), one(L.wo), one(L.w_down)
+        L.w_gate_up = one(L.w_gate_up, il)
+        if il:
+            L.gu_block = 32
+
     def _load(self, path: str) -> None:
         """Load HF-layout safetensors (model.layers.N.self_attn.q_proj.weight ...) and fuse q|k|v and
-        gate|up into the engine's layout."""
+        gate|up into the engine's layout.
+
+        ``mxfp4=True``: bf16 projections are quantised layer by layer; a projection stored pre-quantised — uint8
+        ``<name>.weight`` [N, K / 2] with uint8 ``<name>.weight_scale`` [N, K / 32] in the format of ops/mxfp4.py
+        (``scripts/quantize_mxfp4.py`` writes such files; the project's own convention) — is taken as it is,
+        its shapes checked by tensor name."""
         from safetensors.torch import load_file
 
         files = sorted(Path(path).glob("*.safetensors")) if Path(path).is_dir() else [Path(path)]
@@ -276,6 +326,31 @@ class LlamaModel:
                 out["k_norm"] = req(p + "self_attn.k_norm.weight", (D,))
             return out
 
+        def proj(parts):
+            """One projection from its checkpoint tensors ``[(name, N, K)]``, concatenated along N: the bf16
+            weight, or an ops.Mxfp4Weight when the parts are stored pre-quantised."""
+            packed = [sd[n + ".weight"].dtype == torch.uint8 for n, _, _ in parts]
+            if not any(packed):
+                return torch.cat([t(n + ".weight") for n, _, _ in parts]).contiguous()
+            if not self.mxfp4:
+                raise ValueError(f"{path}: {parts[0][0]}.weight is MXFP4-quantised; load it with mxfp4=True")
+            if not all(packed):
+                raise ValueError(f"{path}: {', '.join(n for n, _, _ in parts)} must all be MXFP4-quantised or none")
+            qs, ss = [], []
+            for n, N, K in parts:
+                for name, shape in ((n + ".weight", (N, K // 2)), (n + ".weight_scale", (N, K // 32))):
+                    if name not in sd:
+                        raise ValueError(f"{path}: {cfg.name} needs {name}, which the checkpoint does not have")
+                    if sd[name].dtype != torch.uint8 or tuple(sd[name].shape) != shape:
+                        raise ValueError(f"{path}: {name} is {sd[name].dtype} {tuple(sd[name].shape)}, {cfg.name} "
+                                         f"expects uint8 {shape}")
+                if bool((sd[n + ".weight_scale"] == 255).any()):
+                    raise ValueError(f"{path}: {n}.weight_scale holds the e8m0 byte 255 (NaN)")
+                qs.append(sd[n + ".weight"].to(dev))
+                ss.append(sd[n + ".weight_scale"].to(dev))
+            return Mxfp4Weight.from_packed(torch.cat(qs), torch.cat(ss), parts[0][0])
+
+        d, F_ = cfg.hidden, cfg.ffn
         self.embed = t("model.embed_tokens.weight")
         self.layers = []
         for i in range(self.cfg.layers):
@@ -283,13 +358,15 @@ class LlamaModel:
             self.layers.append(LayerWeights(
                 **attn_extras(p),
                 attn_norm=t(p + "input_layernorm.weight"),
-                wqkv=torch.cat([t(p + "self_attn.q_proj.weight"), t(p + "self_attn.k_proj.weight"),
-                                t(p + "self_attn.v_proj.weight")]).contiguous(),
-                wo=t(p + "self_attn.o_proj.weight"),
+                wqkv=proj([(p + f"self_attn.{x}_proj", n * D, d) for x, n in
+                           (("q", cfg.heads), ("k", cfg.kv_heads), ("v", cfg.kv_heads))]),
+                wo=proj([(p + "self_attn.o_proj", d, cfg.heads * D)]),
                 mlp_norm=t(p + "post_attention_layernorm.weight"),
-                w_gate_up=torch.cat([t(p + "mlp.gate_proj.weight"), t(p + "mlp.up_proj.weight")]).contiguous(),
-                w_down=t(p + "mlp.down_proj.weight"),
+                w_gate_up=proj([(p + "mlp.gate_proj", F_, d), (p + "mlp.up_proj", F_, d)]),
+                w_down=proj([(p + "mlp.down_proj", d, F_)]),
             ))
+            if self.mxfp4:
+                self._quantise_layer(self.layers[-1])
         self.final_norm = t("model.norm.weight")
         self.lm_head = t("lm_head.weight") if "lm_head.weight" in sd else self.embed
 
@@ -459,7 +536,7 @@ class LlamaModel:
     def _dense_residual(self) -> bool:
         cls = type(self)
         return (cls._attn_out is LlamaModel._attn_out and cls._mlp is LlamaModel._mlp
-                and not getattr(self, "fp8_dense", False))
+                and not getattr(self, "fp8_dense", False) and not getattr(self, "mxfp4", False))
 
     def _proj(self, x, w: torch.Tensor) -> torch.Tensor:
         """Dense projection on the per-shape backend (ops/gemm_plan.py: hipBLASLt, gemm4w or gemm8p); e4m3
@@ -467,6 +544,8 @@ class LlamaModel:
         fp8 GEMM (gemm8g dense or the library, ops.linear_fp8_q)."""
         if isinstance(w, ops.Fp8Weight):
             return ops.linear_fp8(x, w)
+        if isinstance(w, Mxfp4Weight):  # M <= 64: the MXFP4 weight stream; above: dequantise + the bf16 path
+            return ops.linear_mxfp4(x, w, self.mx_scratch, ws=self.g8_ws)
         if self.g8_ws is None:
             return F.linear(x, w)
         return gemm_plan.linear(x, w, ws=self.g8_ws)
@@ -490,6 +569,8 @@ class LlamaModel:
 
     def _act(self, h: torch.Tensor, L) -> torch.Tensor:
         """silu(h Wg^T) * (h Wu^T): the gate|up GEMM with its SwiGLU."""
+        if isinstance(L.w_gate_up, Mxfp4Weight):
+            return ops.swiglu_mxfp4(h, L.w_gate_up, L.gu_block, self.mx_scratch, ws=self.g8_ws)
         if self.g8_ws is None:
             return ops.silu_mul(F.linear(h, L.w_gate_up), block=L.gu_block)
         return gemm_plan.swiglu(h, L.w_gate_up, L.gu_block, ws=self.g8_ws)
@@ -503,7 +584,8 @@ class LlamaModel:
     @property
     def _planned_gemms(self) -> bool:
         """Whether the projections go through ops/gemm_plan.py (the dense bf16 decoder on the GPU)."""
-        return self.g8_ws is not None and isinstance(self.layers[0], LayerWeights) and not self.fp8_dense
+        return (self.g8_ws is not None and isinstance(self.layers[0], LayerWeights) and not self.fp8_dense
+                and not self.mxfp4)
 
     def _chain_unusable(self, M: int) -> Optional[str]:
         """Why a decode step of M rows cannot fold norms, or None when it can; the NormChain is allocated here,

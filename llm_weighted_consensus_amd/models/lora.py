@@ -142,6 +142,18 @@ def check_model_spec(name: str, spec: dict, embedder: bool = False) -> Tuple[str
     from .config import DECODERS
 
     ads = spec.get("adapters")
+    if spec.get("mxfp4"):  # MXFP4 weight-only projections (ops/mxfp4.py): the dense single-GPU decoder only
+        if embedder:
+            raise ValueError(f"embedding model {name}: mxfp4 weights are served on generation models only")
+        if spec.get("fp8"):
+            raise ValueError(f"model {name}: mxfp4 weights do not combine with fp8 weights")
+        if int(spec.get("tp", 1) or 1) > 1:
+            raise ValueError(f"model {name}: mxfp4 weights do not combine with tp > 1")
+        if ads:
+            raise ValueError(f"model {name}: mxfp4 weights do not combine with LoRA adapters")
+        mcfg = DECODERS.get(spec.get("arch"))
+        if mcfg is not None and mcfg.num_experts:
+            raise ValueError(f"model {name}: mxfp4 weights are not supported on MoE decoders ({mcfg.name})")
     if not ads:
         return ()
     if not isinstance(ads, dict):

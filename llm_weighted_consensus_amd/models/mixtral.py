@@ -63,7 +63,9 @@ class MixtralModel(LlamaModel):
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8: bool = False,
                  tp_rank: int = 0, tp_size: int = 1, tp_group=None, ep_rank: int = 0, ep_size: int = 1,
                  ep_group=None, ep_mode: str = "padded", ep_capacity: Optional[int] = None, tp_comm=None,
-                 ep_comm=None):
+                 ep_comm=None, mxfp4: bool = False):
+        if mxfp4:
+            raise ValueError(f"mxfp4 weights are not supported on MoE decoders ({cfg.name})")
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
         if cfg.qkv_bias or cfg.qk_norm:

@@ -86,7 +86,9 @@ class TPLlamaModel(TensorParallel, LlamaModel):
 
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
-                 tp_rank: int = 0, tp_size: int = 1, tp_group=None, tp_comm=None):
+                 tp_rank: int = 0, tp_size: int = 1, tp_group=None, tp_comm=None, mxfp4: bool = False):
+        if mxfp4:
+            raise ValueError("mxfp4 weights do not combine with tensor parallelism (tp > 1)")
         if cfg.num_experts:
             raise ValueError(f"{cfg.name} is a MoE decoder; use MixtralModel")
         if cfg.heads % tp_size or cfg.kv_heads % tp_size or cfg.ffn % tp_size:

@@ -480,6 +480,68 @@ def skinny_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
     return 0 < M <= 64 and K % 2048 == 0 and N % (64 if swiglu else 16) == 0
 
 
+# ---------------------------------------------------------------------------------------------
+# MXFP4 weight-only projections (4-bit weights, bf16 activations): format and host quantiser in ops/mxfp4.py,
+# kernels in csrc/kernels/mxfp4.hip
+
+from .mxfp4 import Mxfp4Weight, check_mxfp4, dequant_mxfp4, quant_mxfp4_weight  # noqa: E402
+
+
+def mxfp4_dequant(w: Mxfp4Weight, out: torch.Tensor) -> torch.Tensor:
+    """The bf16 weight [N, K] of ``w`` into ``out`` (caller-owned, contiguous: safe inside a captured graph),
+    bitwise equal to :func:`dequant_mxfp4`."""
+    kernels().mxfp4_dequant(w.q, w.s, out)
+    return out
+
+
+def skinny_mxfp4_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
+    return 0 < M <= 64 and K % 128 == 0 and N % (64 if swiglu else 16) == 0
+
+
+def skinny_mxfp4(A: torch.Tensor, w: Mxfp4Weight, out: Optional[torch.Tensor] = None,
+                 swiglu: bool = False) -> torch.Tensor:
+    """Decode-sized projection over an MXFP4 weight (csrc/kernels/mxfp4.hip): ``A [M <= 64, K] . W[N, K]^T`` (or
+    ``swiglu`` over a 32-row gate/up interleaved W, output [M, N / 2]); bf16 activations (rows may be strided),
+    fp32 accumulation, bf16 out.  The weight stream of :func:`skinny_gemm` at 4.25 bits per weight.  Needs
+    K % 128 == 0 and N % 16 == 0 (SwiGLU: N % 64 == 0) (:func:`skinny_mxfp4_ok`); other shapes are refused."""
+    if out is None:
+        out = torch.empty(A.shape[0], w.shape[0] // 2 if swiglu else w.shape[0], dtype=torch.bfloat16,
+                          device=A.device)
+    kernels().skinny_mxfp4(A, w.q, w.s, out, 2 if swiglu else 0)
+    return out
+
+
+def _mxfp4_scratch(w: Mxfp4Weight, scratch: torch.Tensor) -> torch.Tensor:
+    N, K = w.shape
+    if scratch.dtype != torch.bfloat16 or not scratch.is_contiguous() or scratch.numel() < N * K:
+        raise ValueError(f"MXFP4 scratch: a contiguous bf16 buffer of at least {N * K} elements, got "
+                         f"{scratch.dtype} x {scratch.numel()}")
+    return mxfp4_dequant(w, scratch.view(-1)[:N * K].view(N, K))
+
+
+def linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight, scratch: torch.Tensor, ws=None) -> torch.Tensor:
+    """x [M, K] . W^T for an MXFP4 weight: the weight-stream kernel up to 64 rows where it takes the shape;
+    otherwise (prefill, mixed steps, large decode buckets) W is dequantised into ``scratch`` — one bf16 buffer
+    the size of the model's largest projection, allocated once by the model and never inside a capture — and
+    the bf16 path of ops/gemm_plan.py runs on it."""
+    if skinny_mxfp4_ok(x.shape[0], w.shape[0], w.shape[1]) and x.stride(1) == 1 and x.stride(0) % 4 == 0:
+        return skinny_mxfp4(x, w)
+    from . import gemm_plan
+
+    return gemm_plan.linear(x, _mxfp4_scratch(w, scratch), ws=ws)
+
+
+def swiglu_mxfp4(x: torch.Tensor, w: Mxfp4Weight, block: int, scratch: torch.Tensor, ws=None) -> torch.Tensor:
+    """silu(x Wg^T) * (x Wu^T) for an MXFP4 gate|up weight whose rows are interleaved in blocks of ``block``
+    (0: [gate; up]); routed as :func:`linear_mxfp4`."""
+    if (block == 32 and skinny_mxfp4_ok(x.shape[0], w.shape[0], w.shape[1], swiglu=True) and x.stride(1) == 1
+            and x.stride(0) % 4 == 0):
+        return skinny_mxfp4(x, w, swiglu=True)
+    from . import gemm_plan
+
+    return gemm_plan.swiglu(x, _mxfp4_scratch(w, scratch), block, ws=ws)
+
+
 def gemm4w(A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, swiglu: bool = False, bias: Optional[torch.Tensor] = None,
            gelu: bool = False, bn: int = 256, chain: "Optional[NormChain]" = None, var: int = 0,

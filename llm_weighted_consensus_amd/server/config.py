@@ -16,6 +16,11 @@ variables configure the local engine:
                     rank / alpha / targets / std describe a random adapter; a PEFT directory
                     (adapter_config.json + adapter_model.safetensors) brings its own.  Dense Llama-family
                     models only: refused with "tp" > 1, "fp8", MoE archs and in LWC_EMBED_MODELS
+                    "mxfp4": true holds the qkv / o / gate|up / down projections as MXFP4 (OCP e2m1 codes, one
+                    e8m0 scale per 32: 4.25 bits per weight, ops/mxfp4.py) with bf16 activations: a bf16
+                    checkpoint is quantised at load, one written by scripts/quantize_mxfp4.py is taken as it
+                    is.  Dense Llama-family models only: refused with "fp8", "tp" > 1, "adapters", MoE archs
+                    and in LWC_EMBED_MODELS
   LWC_EMBED_MODELS  JSON {name: {"arch": "bge-large-en-v1.5", "weights": "random:<seed>" | <path>}}
   LWC_GPU           device index for this process's engine (one process per GPU)
   LWC_GPUS          comma list of devices: serve each model through an EngineGroup (one worker process

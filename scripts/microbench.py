@@ -605,6 +605,147 @@ def skinny_ab(dev):
             del x, ws, acc
 
 
+def mxfp4_ab(dev):
+    """MXFP4 weight-only projections at the Llama-3-8B shapes (profiles/mxfp4.md), arms interleaved in one
+    process, median of 7 rounds, weights rotated over more copies than the last-level cache holds:
+    (a) M <= 64: skinny_mxfp4 vs ops.skinny_gemm on a bf16 weight vs the planner's bf16 choice, us and weight GB/s
+        (each arm's own weight bytes);
+    (b) M > 64: dequantise + GEMM (ops.linear_mxfp4 / swiglu_mxfp4) vs the GEMM alone, and the dequantisation alone;
+    (c) one llama-3-8b random-weight decode step (captured graph) at B in {1, 16, 64}, bf16 vs mxfp4, with the KV
+        blocks LLMEngine's sizing rule (kv_memory_fraction 0.85 of the free memory) gives each.
+    MX_PARTS=a,b,c selects the parts."""
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.llama import KVCache, LlamaModel
+    from llm_weighted_consensus_amd.ops import gemm_plan
+
+    parts = os.environ.get("MX_PARTS", "a,b,c").split(",")
+    shapes = [("qkv", 6144, 4096, False), ("o", 4096, 4096, False), ("gate_up", 28672, 4096, True),
+              ("down", 4096, 14336, False)]
+
+    def rand_mx(N, K):  # timing only: any codes, scales near 2^-6
+        q = torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8)
+        s = torch.randint(117, 125, (N, K // 32), device=dev, dtype=torch.uint8)
+        return ops.Mxfp4Weight.from_packed(q, s)
+
+    def rotating(items):
+        it = [0]
+
+        def nxt():
+            it[0] = (it[0] + 1) % len(items)
+            return items[it[0]]
+        return nxt
+
+    def med(runs, iters):
+        """us per call: each arm captured as one graph of ``iters`` calls (the serving decode step is a captured
+        graph: eager launches of kernels this short time the host, not the device), replays interleaved."""
+        graphs = {}
+        for k, fn in runs.items():
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            graphs[k] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[k]):
+                for _ in range(iters):
+                    fn()
+            graphs[k].replay()
+        torch.cuda.synchronize()
+        t = {k: [] for k in runs}
+        for _ in range(7):
+            for k, g in graphs.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                g.replay()
+                e.record()
+                e.synchronize()
+                t[k].append(s.elapsed_time(e) / iters * 1e3)
+        return {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+
+    for name, N, K, sw in shapes:
+        if not ({"a", "b"} & set(parts)):
+            break
+        nw = max(2, min(16, (768 << 20) // (N * K * 2)))
+        wb = rotating([((torch.rand(N, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16) for _ in range(nw)])
+        wm = rotating([rand_mx(N, K) for _ in range(4 * nw)])  # (a quarter of the bytes each)
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device=dev)
+        mxb, bfb = N * K * (0.5 + 1 / 32), N * K * 2.0
+        for M in ([int(m) for m in os.environ.get("MX_M", "1,8,16,32,64").split(",")] if "a" in parts else []):
+            x = (torch.rand(M, K, device=dev) * 2 - 1).to(torch.bfloat16)
+            gemm_plan.tune(x, wb(), "swiglu" if sw else "plain", 32 if sw else 0)
+            if sw:
+                runs = {"mxfp4": lambda: ops.skinny_mxfp4(x, wm(), swiglu=True),
+                        "gv": lambda: ops.skinny_gemm(x, wb(), swiglu=True),
+                        "planner": lambda: gemm_plan.swiglu(x, wb(), 32)}
+            else:
+                runs = {"mxfp4": lambda: ops.skinny_mxfp4(x, wm()), "gv": lambda: ops.skinny_gemm(x, wb()),
+                        "planner": lambda: gemm_plan.linear(x, wb())}
+            t = med(runs, 20)
+            ch = gemm_plan.choice(M, N, K, "swiglu" if sw else "plain")
+            print(f"mxfp4 (a) {name} {N}x{K} M={M}: mxfp4 {t['mxfp4']:7.1f} us ({mxb / t['mxfp4'] / 1e3:6.0f} GB/s)  "
+                  f"gv {t['gv']:7.1f} us ({bfb / t['gv'] / 1e3:6.0f} GB/s)  planner[{ch}] {t['planner']:7.1f} us "
+                  f"({bfb / t['planner'] / 1e3:6.0f} GB/s)  gv/mxfp4 {t['gv'] / t['mxfp4']:.2f}x", flush=True)
+        for M in ([128, 512, 2048] if "b" in parts else []):
+            x = (torch.rand(M, K, device=dev) * 2 - 1).to(torch.bfloat16)
+            gemm_plan.tune(x, wb(), "swiglu" if sw else "plain", 32 if sw else 0)  # both arms run its choice
+            if sw:
+                runs = {"dq+gemm": lambda: ops.swiglu_mxfp4(x, wm(), 32, scratch),
+                        "gemm": lambda: gemm_plan.swiglu(x, wb(), 32)}
+            else:
+                runs = {"dq+gemm": lambda: ops.linear_mxfp4(x, wm(), scratch), "gemm": lambda: gemm_plan.linear(x, wb())}
+            runs["dq"] = lambda: ops.mxfp4_dequant(wm(), scratch.view(N, K))
+            t = med(runs, 10)
+            print(f"mxfp4 (b) {name} {N}x{K} M={M}: dequant+gemm {t['dq+gemm']:7.1f} us  gemm {t['gemm']:7.1f} us  "
+                  f"dequant alone {t['dq']:6.1f} us ({(mxb + bfb) / t['dq'] / 1e3:5.0f} GB/s read+written)  "
+                  f"+{(t['dq+gemm'] / t['gemm'] - 1) * 100:.0f} %", flush=True)
+        del wb, wm, scratch
+        torch.cuda.empty_cache()
+    if "c" not in parts:
+        return
+    cfg = decoder_config("llama-3-8b")
+    i32 = dict(dtype=torch.int32, device=dev)
+    for label, kw in (("bf16", {}), ("mxfp4", {"mxfp4": True})):
+        torch.cuda.empty_cache()
+        model = LlamaModel(cfg, device=dev, seed=0, max_position=256, **kw)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info(dev)
+        blocks = int(free * 0.85) // KVCache.bytes_per_block(cfg, 16)
+        print(f"mxfp4 (c) llama-3-8b [{label}]: {torch.cuda.memory_allocated(dev) / 2 ** 30:.1f} GiB allocated, "
+              f"{free / 2 ** 30:.1f} GiB free -> {blocks} KV blocks of 16 tokens", flush=True)
+        for B in (1, 16, 64):
+            pos = 32
+            cache = KVCache(cfg, 3 * B, 16, dev)
+            bt = torch.arange(3 * B, **i32).view(B, 3)
+            positions, ctx = torch.full((B,), pos, **i32), torch.full((B,), pos + 1, **i32)
+            slots = (bt[:, 2] * 16).contiguous()
+            tokens = torch.randint(0, cfg.vocab_size, (B,), device=dev).int()
+            model.tune_gemms(B)
+
+            def fwd():
+                return model.decode(tokens, positions, slots, bt, ctx, cache, num_splits=1)
+
+            for _ in range(2):
+                fwd()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fwd()
+            ts = []
+            for _ in range(23):
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                g.replay()
+                e.record()
+                e.synchronize()
+                ts.append(s.elapsed_time(e))
+            ts = sorted(ts[3:])
+            print(f"mxfp4 (c) llama-3-8b [{label}] decode step B={B}: median {ts[len(ts) // 2]:.3f} ms "
+                  f"(min {ts[0]:.3f}, max {ts[-1]:.3f})", flush=True)
+            del g, cache
+        del model
+        torch.cuda.empty_cache()
+
+
 def serve_shapes(dev):
     """Llama-3-8B projections at the serving path's mixed chunked-prefill row counts (2048 prompt rows + the
     decode rows): every backend the planner times, median of 5 interleaved rounds (SERVE_M overrides)."""
@@ -1014,6 +1155,8 @@ def main():
         serve_shapes(dev)
     if "skinny" in a.what:
         skinny_ab(dev)
+    if "mxfp4" in a.what:
+        mxfp4_ab(dev)
     if "lora" in a.what:
         lora_kernels(dev)
     if "lorastep" in a.what:
