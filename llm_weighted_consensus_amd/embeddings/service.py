@@ -89,10 +89,10 @@ def build_embedding_service(name: str, spec: dict, dev) -> "EmbeddingService":
 
     from ..engine.tokenizer import HFTokenizer
     from ..models.bert import BertEncoder
-    from ..models.config import DECODERS, decoder_config, encoder_config
+    from ..models.config import DECODERS, check_variant, decoder_config, encoder_config
 
-    if spec.get("mxfp4"):
-        raise ValueError(f"embedding model {name}: mxfp4 weights are served on generation models only")
+    check_variant(DECODERS.get(spec.get("arch")), mxfp4=bool(spec.get("mxfp4")), adapters=bool(spec.get("adapters")),
+                  embedder=True, who=f"embedding model {name}")
     w = spec.get("weights", "random:0")
     path, seed = (None, int(w.split(":", 1)[1])) if str(w).startswith("random:") else (w, 0)
     dev = torch.device(dev)

@@ -65,6 +65,37 @@ def check_decoder(cfg: DecoderConfig) -> None:
                          "head_dim 128 only")
 
 
+def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool = False, mxfp4: bool = False,
+                  adapters: bool = False, embedder: bool = False, device_type: Optional[str] = None,
+                  who: str = "") -> None:
+    """Refuse the decoder variants that do not combine (the model constructors, ``lora.check_model_spec`` and
+    the embedding service all call this with the facts they know; ``cfg`` None: an arch not registered).
+
+    MXFP4 weight-only projections (ops/mxfp4.py) and LoRA adapters (models/lora.py) each run on the dense
+    single-GPU generation decoder only, not with fp8 weights and not with each other; the adapters on the GPU
+    kernels only (``device_type``, where the caller has a device).  ``who`` prefixes the message."""
+    moe = cfg is not None and bool(cfg.num_experts)
+    for on, what in ((mxfp4, "mxfp4 weights"), (adapters, "LoRA adapters")):
+        if not on:
+            continue
+        why = None
+        if embedder:
+            why = f"{what} are served on generation models only"
+        elif fp8:
+            why = f"{what} do not combine with fp8 weights"
+        elif tp:
+            # (a spec, which has a ``who``, is told by its own key)
+            why = f"{what} do not combine with {'tp > 1' if who else 'tensor parallelism (tp > 1)'}"
+        elif mxfp4 and adapters:
+            why = "mxfp4 weights do not combine with LoRA adapters"
+        elif moe:
+            why = f"{what} are not supported on MoE decoders ({cfg.name})"
+        elif adapters and device_type is not None and device_type != "cuda":
+            why = "LoRA adapters run on the GPU kernels only"
+        if why is not None:
+            raise ValueError(f"{who}: {why}" if who else why)
+
+
 @dataclass(frozen=True)
 class EncoderConfig:
     name: str

@@ -42,7 +42,7 @@ from .. import ops
 from ..ops import blas_tuning, gemm_plan
 from ..ops.mxfp4 import Mxfp4Weight
 from . import step_plan
-from .config import DecoderConfig, check_decoder
+from .config import DecoderConfig, check_decoder, check_variant
 from .step_plan import ChainPlan
 
 
@@ -81,6 +81,17 @@ class LayerWeights:
     k_norm: Optional[torch.Tensor] = None  # [D]  the same for k
 
 
+def _claim_gu_interleave(L: LayerWeights) -> bool:
+    """The gate|up interleave rule, stated once: a GPU layer whose gate|up rows are still in the plain order and
+    pair up in blocks of 32 (2F a multiple of 64) gets them interleaved in blocks of 32, so the GEMM epilogues
+    (gemm8p, gemm8g, the MXFP4 stream) can apply the SwiGLU.  True: ``gu_block`` is now 32 and the caller
+    permutes the rows it holds (``ops.swiglu_interleave``: a bf16 weight, or MXFP4 codes and scales)."""
+    if L.gu_block != 0 or L.w_gate_up.shape[0] % 64 != 0:
+        return False
+    L.gu_block = 32
+    return True
+
+
 class KVCache:
     """One flat bf16 pool for all layers: [L, 2, num_blocks, Hkv*BS*D]; per-layer K view
     [NB, Hkv, BS, D] and 4-token-interleaved V view [NB, Hkv, BS/4, D, 4] (see attention_decode.hip)."""
@@ -113,38 +124,30 @@ class _NullCache:
 
 
 class LlamaModel:
+    # What a subclass is, said by the subclass: the dense decoder on one rank adds its o / down projections into
+    # the residual stream itself; the tensor-parallel and MoE subclasses reduce / route them first (False there)
+    single_rank_dense = True
+    tp_size = 1
+
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
                  fold_norms: bool = True, lora=None, mxfp4: bool = False):
         check_decoder(cfg)  # shapes the kernels do not serve are refused here, by arch name
-        # MXFP4 weight-only projections (ops/mxfp4.py): qkv / o / gate|up / down as 4-bit codes with one e8m0
-        # scale per 32, bf16 activations; the dense single-GPU decoder only.  On a CPU device the model holds the
-        # dequantised bf16 weights (the same function, through F.linear)
-        if mxfp4:
-            if cfg.num_experts:
-                raise ValueError(f"mxfp4 weights are not supported on MoE decoders ({cfg.name})")
-            if type(self) is not LlamaModel:
-                raise ValueError("mxfp4 weights do not combine with tensor parallelism (tp > 1)")
-            if fp8_dense:
-                raise ValueError("mxfp4 weights do not combine with fp8 weights")
-            if lora is not None:
-                raise ValueError("mxfp4 weights do not combine with LoRA adapters")
-        self.mxfp4 = bool(mxfp4)
-        self.mx_scratch: Optional[torch.Tensor] = None  # bf16, the largest projection (ops.linear_mxfp4)
-        if cfg.num_experts and type(self) is LlamaModel:
-            raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
-        # LoRA adapters (``lora``: a list of models/lora.py Adapters, laid out here once for this model's weights
-        # and device, or a LoraSet): rows of one batch carry different adapters (``lora_ids``).  The dense
-        # single-GPU bf16 decoder only, with unfolded norms: the adapters read the normalised rows
-        if lora is not None:
-            if type(self) is not LlamaModel or cfg.num_experts:
-                raise ValueError("LoRA adapters: only the dense single-GPU Llama decoder (no tensor parallelism, no MoE)")
-            if fp8_dense:
-                raise ValueError("LoRA adapters do not combine with fp8 weights")
-            if torch.device(device).type != "cuda":
-                raise ValueError("LoRA adapters run on the GPU kernels only")
-            fold_norms = False
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
+        check_variant(cfg, tp=self.tp_size > 1, fp8=fp8_dense, mxfp4=mxfp4, adapters=lora is not None,
+                      device_type=self.device.type)
+        # The variant, stated once; everything below reads these (and the class's ``single_rank_dense``).
+        # "mxfp4" (ops/mxfp4.py): qkv / o / gate|up / down as 4-bit codes with one e8m0 scale per 32, bf16
+        # activations; on a CPU device the model holds the dequantised bf16 weights (the same function, through
+        # F.linear).  "fp8" (BASELINE config 5): the same projections (a MoE decoder's: attention and experts) in
+        # e4m3 with per-channel scales, activations quantised per row; lm_head stays bf16.  The dense decoder's
+        # fp8 exists on the GPU only: on a CPU device it stays "bf16"
+        self.moe = bool(cfg.num_experts)
+        self.on_gpu = self.device.type == "cuda"
+        self.weight_format = "mxfp4" if mxfp4 else "fp8" if fp8_dense and (self.on_gpu or self.moe) else "bf16"
+        if self.moe and self.single_rank_dense:
+            raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
+        self.mx_scratch: Optional[torch.Tensor] = None  # bf16, the largest projection (ops.linear_mxfp4)
         self.cos, self.sin = rope_tables(cfg, self.device, max_position)
         if weights_path:
             self._load(weights_path)
@@ -152,31 +155,25 @@ class LlamaModel:
             self._random_init(seed)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
         self.g8_ws = None
-        if self.mxfp4 and self.device.type == "cuda":
+        if self.mxfp4 and self.on_gpu:
             # one dequantisation buffer for every projection past 64 rows, allocated here: never inside a capture
             n = max(math.prod(w.shape) for L in self.layers for w in (L.wqkv, L.wo, L.w_gate_up, L.w_down))
             self.mx_scratch = torch.empty(n, dtype=torch.bfloat16, device=self.device)
             torch.cuda.empty_cache()
-        # fp8 configurations (BASELINE config 5: the e5-mistral embedder): the qkv / o / gate|up / down
-        # projections in e4m3 with per-channel scales, activations quantised per row; lm_head stays bf16
-        self.fp8_dense = bool(fp8_dense) and self.device.type == "cuda"
-        if self.fp8_dense:
-            for L in self.layers:
-                if isinstance(L, LayerWeights):
+        if self.on_gpu:
+            # the dense layers' GPU layout (after a TP subclass cut its shard: shard_dense_layer reads the plain
+            # row order): gate|up interleaved for the SwiGLU epilogues, then the fp8 conversion.  (MXFP4 layers
+            # were laid out as they were built, MoE layers in MixtralModel._shard_layer.)
+            for L in () if self.moe else self.layers:
+                if self.fp8_dense:
                     L.wqkv, L.wo = ops.Fp8Weight(L.wqkv), ops.Fp8Weight(L.wo)
-                    if L.gu_block == 0 and L.w_gate_up.shape[0] % 64 == 0:
-                        # gate|up interleaved in blocks of 32: gemm8g's epilogue applies the SwiGLU
-                        L.w_gate_up, L.gu_block = ops.swiglu_interleave(L.w_gate_up), 32
-                    L.w_gate_up, L.w_down = ops.Fp8Weight(L.w_gate_up), ops.Fp8Weight(L.w_down)
-            torch.cuda.empty_cache()
-        if self.device.type == "cuda":
-            # gemm8p (ops/gemm_plan.py): the gate|up rows interleaved in blocks of 32 so its epilogue can
-            # apply SwiGLU; a stream-K workspace owned by the model (never allocated inside a capture)
-            for L in self.layers:
-                if (isinstance(L, LayerWeights) and not self.fp8_dense and L.gu_block == 0
-                        and L.w_gate_up.shape[0] % 64 == 0):
+                if _claim_gu_interleave(L):
                     L.w_gate_up = ops.swiglu_interleave(L.w_gate_up)
-                    L.gu_block = 32
+                if self.fp8_dense:
+                    L.w_gate_up, L.w_down = ops.Fp8Weight(L.w_gate_up), ops.Fp8Weight(L.w_down)
+            if self.fp8_dense:
+                torch.cuda.empty_cache()
+            # gemm8p's stream-K workspace, owned by the model (never allocated inside a capture)
             self.g8_ws = ops.new_gemm8p_workspace(self.device)
             blas_tuning.enable()  # offline-tuned library solutions: only with LWC_TUNED_BLAS=1 (off by default)
         # folded RMSNorm (module docstring): the plain dense bf16 decoder on the GPU
@@ -185,6 +182,9 @@ class LlamaModel:
         self.final_norm_weight: Optional[torch.Tensor] = None  # the final norm's weight once lm_head holds it
         self.chain: Optional[ops.NormChain] = None
         self.chain_m: dict = {}  # decode batch M -> the step's chain plan, as a dict (step_plan.ChainPlan.from_dict)
+        # LoRA adapters (``lora``: a list of models/lora.py Adapters, laid out here once for this model's weights
+        # and device, or a LoraSet): rows of one batch carry different adapters (``lora_ids``).  With unfolded
+        # norms: the adapters read the normalised rows
         self.lora = None
         if lora is not None:
             from .lora import LoraSet
@@ -196,9 +196,8 @@ class LlamaModel:
             self.lora = lora
         self.pinned: dict = {}  # decode batch M -> a fixed step plan (pin_step_plan): nothing is timed at M
         # ``fold_norms=False``: models that never decode through lm_head (the decoder-as-embedder) skip it
-        if (fold_norms and self.device.type == "cuda" and not self.fp8_dense and not self.mxfp4
-                and type(self) is LlamaModel
-                and os.environ.get("LWC_NORM_FOLD", "1") != "0" and isinstance(self.layers[0], LayerWeights)):
+        if (fold_norms and self.lora is None and self.on_gpu and self._dense_residual
+                and os.environ.get("LWC_NORM_FOLD", "1") != "0"):
             self._fold_norms()
 
     def _fold_norms(self) -> None:
@@ -269,21 +268,16 @@ class LlamaModel:
         permutation, so it applies to the codes and scales directly.  Called as each layer is built, so at most
         one layer's bf16 projections are alive.  On a CPU device the layer holds the dequantised bf16 tensors in
         the plain row order."""
-        gpu = self.device.type == "cuda"
-
         def one(w, interleave=False):
             if isinstance(w, Mxfp4Weight):
                 if interleave:
                     w = Mxfp4Weight.from_packed(ops.swiglu_interleave(w.q), ops.swiglu_interleave(w.s))
             else:
                 w = Mxfp4Weight(ops.swiglu_interleave(w) if interleave else w)
-            return w if gpu else w.dequant()
+            return w if self.on_gpu else w.dequant()
 
-        il = gpu and L.gu_block == 0 and L.w_gate_up.shape[0] % 64 == 0
         L.wqkv, L.wo, L.w_down = one(L.wqkv), one(L.wo), one(L.w_down)
-        L.w_gate_up = one(L.w_gate_up, il)
-        if il:
-            L.gu_block = 32
+        L.w_gate_up = one(L.w_gate_up, self.on_gpu and _claim_gu_interleave(L))
 
     def _load(self, path: str) -> None:
         """Load HF-layout safetensors (model.layers.N.self_attn.q_proj.weight ...) and fuse q|k|v and
@@ -432,72 +426,70 @@ class LlamaModel:
         the weight of the last norm (default ``self.final_norm``; ones once it is folded into lm_head).
         ``lora_ids`` (int32 per row, -1 = none; models built with ``lora=``): each row's adapter is added to
         every projection it targets, after the base GEMM and in place (:meth:`_lora_add`)."""
-        cfg = self.cfg
-        T = x_res.shape[0]
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        # Dense single-rank layers add the o / down projections into the residual stream inside the GEMM
-        # (gemm_plan.linear_add_), so the norms that follow only read x_res and write h.  Subclasses that
-        # reduce the projections across ranks or route them through experts use the separate
-        # residual-add + norm kernel.
-        fused = self._dense_residual and self.g8_ws is not None
-        # fp8 projections: the norms feeding them also emit the per-row e4m3 activation (ops.QAct) in the
-        # same pass, so no separate quantisation kernel re-reads the normalised rows
-        qn = isinstance(self.layers[0].wqkv, ops.Fp8Weight)
-        if qn:
-            h = ops.rmsnorm_quant_fp8(x_res, self.layers[0].attn_norm, cfg.rms_eps)
-        else:
-            h = ops.rmsnorm(x_res, self.layers[0].attn_norm, cfg.rms_eps)
+        T, Hq, D = x_res.shape[0], self.cfg.heads, self.cfg.head_dim
+        # Two seams carry every variant (the rest of the layer is one body):
+        # how a projection joins the residual stream — the dense single-rank bf16 layers on the GPU add o / down
+        # inside the GEMM (gemm_plan.linear_add_; then the adapters), so the norm that follows only reads x_res;
+        # every other variant (fp8, MXFP4, CPU, and the subclasses that reduce the projection across ranks or
+        # route it through experts in _attn_out / _mlp) hands the projection's output to the norm kernel, which
+        # adds it (``residual=``) — and which norm runs (:meth:`_norm`)
+        fused = self._dense_residual and self.on_gpu
         lo = self.lora if lora_ids is not None else None
         if lo is not None and not fused:
             raise RuntimeError("LoRA adapters need the dense fused-residual layer path")
+        nl = len(self.layers)
+
+        def add_norm(name, inp, separate, norm_w, feeds):
+            if not fused:
+                return self._norm(separate(inp, L), norm_w, feeds, residual=x_res)
+            gemm_plan.linear_add_(inp, L.wo if name == "o" else L.w_down, x_res, ws=self.g8_ws)
+            if lo is not None:
+                self._lora_add(x_res, inp, li, name, lora_ids)
+            return self._norm(x_res, norm_w, feeds)
+
+        h = self._norm(x_res, self.layers[0].attn_norm, "attn")
         for li, L in enumerate(self.layers):
+            last = li + 1 == nl
             qkv = self._proj(h, L.wqkv)
             if lo is not None:
                 self._lora_add(qkv, h, li, "qkv", lora_ids)
             self._rope_kv_write(qkv, L, positions, cache.k[li], cache.v[li], slots, rope_q)
             attn = attn_fn(qkv, li)
-            if keep is not None and li + 1 == len(self.layers):
+            if keep is not None and last:
                 attn = attn.index_select(keep) if isinstance(attn, ops.MXAct) else \
                     attn.reshape(T, Hq * D).index_select(0, keep)
                 x_res = x_res.index_select(0, keep)
                 T = x_res.shape[0]
                 if lo is not None:
                     lora_ids = lora_ids.index_select(0, keep)
-            nxt = (self.layers[li + 1].attn_norm if li + 1 < len(self.layers) else
-                   self.final_norm if final_norm is None else final_norm)
-            if fused and lo is not None:
-                a2 = attn.view(T, Hq * D)
-                gemm_plan.linear_add_(a2, L.wo, x_res, ws=self.g8_ws)
-                self._lora_add(x_res, a2, li, "o", lora_ids)
-                h = ops.rmsnorm(x_res, L.mlp_norm, cfg.rms_eps)
-                if lo.adapts_gate_up:  # the adapters add to the pre-activation: no fused SwiGLU epilogue
-                    gu = self._proj(h, L.w_gate_up)
-                    self._lora_add(gu, h, li, "gate_up", lora_ids)
-                    act = ops.silu_mul(gu, block=L.gu_block)
-                else:
-                    act = self._act(h, L)
-                gemm_plan.linear_add_(act, L.w_down, x_res, ws=self.g8_ws)
-                self._lora_add(x_res, act, li, "down", lora_ids)
-                h = ops.rmsnorm(x_res, nxt, cfg.rms_eps)
-            elif fused:
-                gemm_plan.linear_add_(attn.view(T, Hq * D), L.wo, x_res, ws=self.g8_ws)
-                h = ops.rmsnorm(x_res, L.mlp_norm, cfg.rms_eps)
-                gemm_plan.linear_add_(self._act(h, L), L.w_down, x_res, ws=self.g8_ws)
-                h = ops.rmsnorm(x_res, nxt, cfg.rms_eps)
-            elif qn:
-                o = self._attn_out(attn if isinstance(attn, ops.MXAct) else attn.view(T, Hq * D), L)
-                h = ops.rmsnorm_quant_fp8(o, L.mlp_norm, cfg.rms_eps, residual=x_res, keep_bf16=self._mlp_reads_bf16)
-                down = self._mlp(h, L)
-                if li + 1 < len(self.layers):
-                    h = ops.rmsnorm_quant_fp8(down, nxt, cfg.rms_eps, residual=x_res)
-                else:  # the final norm feeds the bf16 lm_head / pooling
-                    h = ops.rmsnorm(down, nxt, cfg.rms_eps, residual=x_res)
+            if not isinstance(attn, ops.MXAct):
+                attn = attn.view(T, Hq * D)
+            h = add_norm("o", attn, self._attn_out, L.mlp_norm, "mlp")
+            if not fused:
+                act = h  # _mlp holds gate|up and down
+            elif lo is not None and lo.adapts_gate_up:  # the adapters add to the pre-activation: no fused SwiGLU
+                gu = self._proj(h, L.w_gate_up)
+                self._lora_add(gu, h, li, "gate_up", lora_ids)
+                act = ops.silu_mul(gu, block=L.gu_block)
             else:
-                o = self._attn_out(attn.view(T, Hq * D), L)
-                h = ops.rmsnorm(o, L.mlp_norm, cfg.rms_eps, residual=x_res)
-                down = self._mlp(h, L)
-                h = ops.rmsnorm(down, nxt, cfg.rms_eps, residual=x_res)
+                act = self._act(h, L)
+            if last:  # the final norm feeds the bf16 lm_head / pooling
+                nxt, feeds = self.final_norm if final_norm is None else final_norm, "out"
+            else:
+                nxt, feeds = self.layers[li + 1].attn_norm, "attn"
+            h = add_norm("down", act, self._mlp, nxt, feeds)
         return h
+
+    def _norm(self, x, w: torch.Tensor, feeds: str, **kw):
+        """RMSNorm of ``x`` (+ ``residual=``, updated in place) for what it ``feeds``: "attn" / "mlp" — fp8
+        projections: the norm also emits the per-row e4m3 activation (ops.QAct) in the same pass, so no separate
+        quantisation kernel re-reads the normalised rows (the MLP's with its bf16 rows where ``_mlp_reads_bf16``);
+        "out" — the bf16 lm_head / pooling, and every norm of the other weight formats: the bf16 kernel."""
+        if self.weight_format != "fp8" or feeds == "out":
+            return ops.rmsnorm(x, w, self.cfg.rms_eps, **kw)
+        if feeds == "mlp":
+            kw["keep_bf16"] = self._mlp_reads_bf16
+        return ops.rmsnorm_quant_fp8(x, w, self.cfg.rms_eps, **kw)
 
     def _rope_kv_write(self, qkv: torch.Tensor, L, positions, k_cache, v_cache, slots, rope_q: bool) -> None:
         """RoPE + the paged KV write of one layer, in place on ``qkv``: the Qwen kernel when the layer carries a
@@ -505,7 +497,7 @@ class LlamaModel:
         rope_kv_write.  q must leave here biased and normalised also on pure decode steps, where the attention
         kernels rotate it as they load it."""
         cfg = self.cfg
-        bias, qn, kn = getattr(L, "bqkv", None), getattr(L, "q_norm", None), getattr(L, "k_norm", None)
+        bias, qn, kn = L.bqkv, L.q_norm, L.k_norm
         if bias is None and qn is None and kn is None:
             ops.rope_kv_write(qkv, positions, self.cos, self.sin, k_cache, v_cache, cfg.heads, cfg.kv_heads,
                               cfg.head_dim, slots=slots, rope_q=rope_q)
@@ -528,15 +520,17 @@ class LlamaModel:
     def _attn_mx(self) -> bool:
         """Whether the attention kernels (decode cascade, prefill) hand the o projection an MX activation: fp8 o weights on gemm8g
         (head_dim 128, every head one 128-wide K slice); LWC_ATTN_MX=0 keeps bf16 + the row quantisation."""
-        L = self.layers[0]
-        return (os.environ.get("LWC_ATTN_MX", "1") != "0" and isinstance(L.wo, ops.Fp8Weight)
-                and self.cfg.head_dim == 128 and ops.FP8_GEMM != "blas" and L.wo.q.shape[0] % 8 == 0)
+        return (os.environ.get("LWC_ATTN_MX", "1") != "0" and self.weight_format == "fp8"
+                and self.cfg.head_dim == 128 and ops.FP8_GEMM != "blas" and self.layers[0].wo.q.shape[0] % 8 == 0)
+
+    # the constructor's flags, as the engine and the tests read them
+    fp8_dense = property(lambda self: self.weight_format == "fp8" and not self.moe)
+    mxfp4 = property(lambda self: self.weight_format == "mxfp4")
 
     @property
     def _dense_residual(self) -> bool:
-        cls = type(self)
-        return (cls._attn_out is LlamaModel._attn_out and cls._mlp is LlamaModel._mlp
-                and not getattr(self, "fp8_dense", False) and not getattr(self, "mxfp4", False))
+        """Whether o / down are plain bf16 projections this rank adds to the residual stream by itself."""
+        return self.single_rank_dense and self.weight_format == "bf16"
 
     def _proj(self, x, w: torch.Tensor) -> torch.Tensor:
         """Dense projection on the per-shape backend (ops/gemm_plan.py: hipBLASLt, gemm4w or gemm8p); e4m3
@@ -546,7 +540,7 @@ class LlamaModel:
             return ops.linear_fp8(x, w)
         if isinstance(w, Mxfp4Weight):  # M <= 64: the MXFP4 weight stream; above: dequantise + the bf16 path
             return ops.linear_mxfp4(x, w, self.mx_scratch, ws=self.g8_ws)
-        if self.g8_ws is None:
+        if not self.on_gpu:
             return F.linear(x, w)
         return gemm_plan.linear(x, w, ws=self.g8_ws)
 
@@ -571,7 +565,7 @@ class LlamaModel:
         """silu(h Wg^T) * (h Wu^T): the gate|up GEMM with its SwiGLU."""
         if isinstance(L.w_gate_up, Mxfp4Weight):
             return ops.swiglu_mxfp4(h, L.w_gate_up, L.gu_block, self.mx_scratch, ws=self.g8_ws)
-        if self.g8_ws is None:
+        if not self.on_gpu:
             return ops.silu_mul(F.linear(h, L.w_gate_up), block=L.gu_block)
         return gemm_plan.swiglu(h, L.w_gate_up, L.gu_block, ws=self.g8_ws)
 
@@ -584,8 +578,7 @@ class LlamaModel:
     @property
     def _planned_gemms(self) -> bool:
         """Whether the projections go through ops/gemm_plan.py (the dense bf16 decoder on the GPU)."""
-        return (self.g8_ws is not None and isinstance(self.layers[0], LayerWeights) and not self.fp8_dense
-                and not self.mxfp4)
+        return self.on_gpu and not self.moe and self.weight_format == "bf16"
 
     def _chain_unusable(self, M: int) -> Optional[str]:
         """Why a decode step of M rows cannot fold norms, or None when it can; the NormChain is allocated here,
@@ -761,7 +754,7 @@ class LlamaModel:
         projection on its fastest hand-written core with the whole norm chain folded.  {} when nothing was
         tuned at M."""
         keys = self._plan_keys(M)
-        if self.g8_ws is None or not any(k in gemm_plan._CHOICE for k in keys.values()):
+        if not self.on_gpu or not any(k in gemm_plan._CHOICE for k in keys.values()):
             return {}
         return step_plan.step_plans({n: gemm_plan._CHOICE.get(k) for n, k in keys.items()}, self._own_backends(M),
                                     self.chain_m.get(M), self._chain_timings(M))

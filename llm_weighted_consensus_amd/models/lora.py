@@ -139,34 +139,16 @@ def check_model_spec(name: str, spec: dict, embedder: bool = False) -> Tuple[str
     """The adapter names of a server model spec, refusing the combinations adapters do not run in (tensor
     parallelism, MoE decoders, fp8 weights, embedding models) and malformed adapter entries: raised when the
     server is configured, before any weight is loaded."""
-    from .config import DECODERS
+    from .config import DECODERS, check_variant
 
     ads = spec.get("adapters")
-    if spec.get("mxfp4"):  # MXFP4 weight-only projections (ops/mxfp4.py): the dense single-GPU decoder only
-        if embedder:
-            raise ValueError(f"embedding model {name}: mxfp4 weights are served on generation models only")
-        if spec.get("fp8"):
-            raise ValueError(f"model {name}: mxfp4 weights do not combine with fp8 weights")
-        if int(spec.get("tp", 1) or 1) > 1:
-            raise ValueError(f"model {name}: mxfp4 weights do not combine with tp > 1")
-        if ads:
-            raise ValueError(f"model {name}: mxfp4 weights do not combine with LoRA adapters")
-        mcfg = DECODERS.get(spec.get("arch"))
-        if mcfg is not None and mcfg.num_experts:
-            raise ValueError(f"model {name}: mxfp4 weights are not supported on MoE decoders ({mcfg.name})")
+    check_variant(DECODERS.get(spec.get("arch")), tp=int(spec.get("tp", 1) or 1) > 1, fp8=bool(spec.get("fp8")),
+                  mxfp4=bool(spec.get("mxfp4")), adapters=bool(ads), embedder=embedder,
+                  who=f"embedding model {name}" if embedder else f"model {name}")
     if not ads:
         return ()
     if not isinstance(ads, dict):
         raise ValueError(f"model {name}: \"adapters\" must map adapter names to their specs")
-    if embedder:
-        raise ValueError(f"embedding model {name}: LoRA adapters are served on generation models only")
-    if int(spec.get("tp", 1) or 1) > 1:
-        raise ValueError(f"model {name}: LoRA adapters do not combine with tp > 1")
-    if spec.get("fp8"):
-        raise ValueError(f"model {name}: LoRA adapters do not combine with fp8 weights")
-    cfg = DECODERS.get(spec.get("arch"))
-    if cfg is not None and cfg.num_experts:
-        raise ValueError(f"model {name}: LoRA adapters are not supported on MoE decoders ({cfg.name})")
     if len(ads) > MAX_ADAPTERS:
         raise ValueError(f"model {name}: {len(ads)} adapters, at most {MAX_ADAPTERS} per model")
     for an, aspec in ads.items():

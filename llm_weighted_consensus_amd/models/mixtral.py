@@ -40,8 +40,9 @@ import torch
 
 from .. import ops
 from ..ops import gemm_plan
-from .config import DecoderConfig
+from .config import DecoderConfig, check_variant
 from .llama import LlamaModel
+from .tp import TensorParallel
 
 
 @dataclass
@@ -56,16 +57,22 @@ class MoELayerWeights:
     s13: Optional[torch.Tensor]   # fp8 per-channel scales [E, 2F_local]
     s2: Optional[torch.Tensor]    # [E, d]
     gu_block: int = 0             # >0: w13 rows interleave gate|up in blocks of this size (fp8 path)
+    # the Qwen attention block's fields (LayerWeights): no MoE decoder has them, the constructor refuses the configs
+    bqkv: None = None
+    q_norm: None = None
+    k_norm: None = None
 
 
-class MixtralModel(LlamaModel):
+class MixtralModel(TensorParallel, LlamaModel):
+    single_rank_dense = False
+    fp8 = property(lambda self: self.weight_format == "fp8")  # (LlamaModel states it: ``fp8_dense=fp8``)
+
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8: bool = False,
                  tp_rank: int = 0, tp_size: int = 1, tp_group=None, ep_rank: int = 0, ep_size: int = 1,
                  ep_group=None, ep_mode: str = "padded", ep_capacity: Optional[int] = None, tp_comm=None,
                  ep_comm=None, mxfp4: bool = False):
-        if mxfp4:
-            raise ValueError(f"mxfp4 weights are not supported on MoE decoders ({cfg.name})")
+        check_variant(cfg, tp=tp_size > 1, fp8=fp8, mxfp4=mxfp4)
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
         if cfg.qkv_bias or cfg.qk_norm:
@@ -84,13 +91,13 @@ class MixtralModel(LlamaModel):
                 raise ValueError(f"ep_group has {self.ep.W} ranks, ep_size is {ep_size}")
         if cfg.heads % tp_size or cfg.kv_heads % tp_size or cfg.ffn % tp_size:
             raise ValueError(f"tp_size {tp_size} must divide heads, kv_heads and ffn")
-        self.fp8, self.tp_rank, self.tp_size, self.tp_group = fp8, tp_rank, tp_size, tp_group
+        self.tp_rank, self.tp_size, self.tp_group = tp_rank, tp_size, tp_group
         # C3 transport: a parallel.allreduce.CustomAllReduce (IPC peer buffers, one graph-capturable kernel)
         # or None for the process group's all-reduce (RCCL / gloo; not capturable)
         self.tp_comm = tp_comm
         self.full_cfg = cfg
         super().__init__(cfg, device=device, dtype=dtype, seed=seed, weights_path=weights_path,
-                         max_position=max_position)
+                         max_position=max_position, fp8_dense=fp8)
         # the attention kernels see the per-rank head counts
         if tp_size > 1:
             from dataclasses import replace
@@ -102,7 +109,7 @@ class MixtralModel(LlamaModel):
         """The bf16 vocabulary projection is the MoE decoder's one dense bf16 GEMM (attention projections and
         experts are fp8, planned per shape in ops.linear_fp8_q): time the library against the hand-written
         cores at decode batch M before the bucket's graph is captured (ops/gemm_plan.py)."""
-        if lm_head and only is None and self.g8_ws is not None and not isinstance(self.lm_head, ops.Fp8Weight):
+        if lm_head and only is None and self.on_gpu and not isinstance(self.lm_head, ops.Fp8Weight):
             x = torch.randn(M, self.cfg.hidden, device=self.device).to(self.dtype)
             gemm_plan.tune(x, self.lm_head, ws=self.g8_ws, bucket=bucket)
 
@@ -188,29 +195,9 @@ class MixtralModel(LlamaModel):
         self.lm_head = t("lm_head.weight") if "lm_head.weight" in sd else self.embed
 
     # ------------------------------------------------------------------ forward pieces
-    def _all_reduce(self, x: torch.Tensor) -> torch.Tensor:
-        if self.tp_size > 1:
-            if self.tp_comm is not None:
-                return self.tp_comm.all_reduce_(x)
-            from ..parallel import dist as pdist
-
-            pdist.all_reduce_(x, group=self.tp_group)
-        return x
-
-    def _comms(self):
-        return [c for c in (self.tp_comm, self.ep.comm if self.ep is not None else None)
-                if c is not None and hasattr(c, "arm")]
-
-    def comm_arm(self) -> None:
-        """Queue the asynchronous readback of the TP all-reduce's / EP all-to-all's error word (after a
-        step's launch)."""
-        for c in self._comms():
-            c.arm()
-
-    def comm_poll(self) -> None:
-        """Raise parallel.allreduce.CommFailure if a completed readback shows a peer never arrived."""
-        for c in self._comms():
-            c.poll()
+    def _comms(self):  # the TP all-reduce's error word and the EP all-to-all's
+        ep = self.ep.comm if self.ep is not None else None
+        return super()._comms() + ([ep] if ep is not None and hasattr(ep, "arm") else [])
 
     @property
     def graph_safe(self) -> bool:

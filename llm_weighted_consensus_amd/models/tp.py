@@ -18,7 +18,7 @@ from typing import Optional
 
 import torch
 
-from .config import DecoderConfig
+from .config import DecoderConfig, check_variant
 from .llama import LayerWeights, LlamaModel
 
 
@@ -84,11 +84,12 @@ class TPLlamaModel(TensorParallel, LlamaModel):
     """Dense decoder (Llama-3 / Mistral) over ``tp_size`` ranks: this rank's attention heads and FFN
     columns, an all-reduce after o and after down (see the module docstring)."""
 
+    single_rank_dense = False
+
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
                  tp_rank: int = 0, tp_size: int = 1, tp_group=None, tp_comm=None, mxfp4: bool = False):
-        if mxfp4:
-            raise ValueError("mxfp4 weights do not combine with tensor parallelism (tp > 1)")
+        check_variant(cfg, tp=True, mxfp4=mxfp4)  # (this class is the tensor-parallel decoder, at any tp_size)
         if cfg.num_experts:
             raise ValueError(f"{cfg.name} is a MoE decoder; use MixtralModel")
         if cfg.heads % tp_size or cfg.kv_heads % tp_size or cfg.ffn % tp_size:

@@ -70,8 +70,7 @@ def test_step_plans_candidates_and_apply(monkeypatch):
 
     m = LlamaModel.__new__(LlamaModel)
     m.cfg = decoder_config("llama-3-8b")
-    m.g8_ws = object()
-    m.fp8_dense = False
+    m.on_gpu, m.weight_format, m.moe = True, "bf16", False
     m.chain = type("Ch", (), {"max_rows": 8192})()
     M = 4096
     keys = m._plan_keys(M)

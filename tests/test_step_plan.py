@@ -9,6 +9,7 @@ import torch
 
 from llm_weighted_consensus_amd.models import llama, step_plan
 from llm_weighted_consensus_amd.models.step_plan import ChainPlan
+from tests.op_recorder import Recorder
 
 PRODUCERS = ("plain", "own32", "own64", "sumsq")
 KEYS = ("attn", "mlp", "final", "qkv_bn", "qkv_var", "gu_var", "lm_var", "lm_split", "o", "down")
@@ -149,35 +150,20 @@ def test_pin_step_plan_rejects_a_bad_plan_at_once():
     assert list(m.pinned) == [4096]
 
 
-class _Recorder:
-    """Stands in for the ``ops`` / ``gemm_plan`` modules in models/llama.py: logs every call, returns ``ret``."""
-    Fp8Weight = type("Fp8Weight", (), {})
-
-    def __init__(self, log, ret):
-        self._log, self._ret = log, ret
-
-    def split_plan(self, *a):
-        return (2, 0)
-
-    def __getattr__(self, name):
-        def call(*a, **kw):
-            self._log.append((name, kw))
-            return self._ret
-        return call
-
-
 def test_chain_layers_never_reads_stale_partials(accepted, monkeypatch):
     """Three layers (the first, an inner and the last differ).  Every row-scaled consumer (gemm4w with ``chain=``
     and no residual) must follow a producer of partials (rms_rowsumsq, or a residual gemm4w with ``chain=``) with
     no update of the residual stream in between."""
     x = torch.zeros(1, 1)
     log = []
-    rec = _Recorder(log, x)
+    rec = Recorder(log, x)
     monkeypatch.setattr(llama, "ops", rec)
     monkeypatch.setattr(llama, "gemm_plan", rec)
     m = llama.LlamaModel.__new__(llama.LlamaModel)
     m.cfg = type("Cfg", (), {"heads": 1, "kv_heads": 1, "head_dim": 1, "hidden": 1, "rms_eps": 1e-5})()
-    m.layers = [type("L", (), {"wqkv": x, "wo": x, "w_gate_up": x, "w_down": x, "gu_block": 32})() for _ in range(3)]
+    m.layers = [type("L", (), {"wqkv": x, "wo": x, "w_gate_up": x, "w_down": x, "gu_block": 32, "bqkv": None,
+                               "q_norm": None, "k_norm": None})() for _ in range(3)]
+    m.on_gpu, m.weight_format, m.moe = True, "bf16", False
     m.chain, m.g8_ws, m.final_norm, m.lm_head, m.cos, m.sin = object(), object(), x, x, x, x
     cache = type("Cache", (), {"k": [x] * 3, "v": [x] * 3})()
     for d in accepted:
