@@ -44,8 +44,8 @@
 // XCD x taking wpx consecutive tiles of the grouped (gm m-tiles) order, so its tiles share operand panels
 // in its L2.  No stream-K: the planner (ops/gemm_plan.py) gives shapes with a ragged last round to
 // gemm8p's stream-K or picks BN = 192 (qkv at M = 4096: 512 tiles = 2 whole rounds instead of 1.5).
-// Epilogue: accumulators -> bf16 (SwiGLU / bias / GELU in fp32 registers) -> LDS -> 16 B row stores (+
-// residual read in the same pass).
+// Epilogue: accumulators -> bf16 (SwiGLU / bias / GELU in fp32 registers) -> LDS -> 16 B row stores; the
+// residual epilogue stages fp32 (two 64-row halves) and adds the residual before the one bf16 rounding.
 //
 // RMSNorm folded into the projections (the decode chain, models/llama.py): rmsnorm(x) . W^T =
 // diag(1/rms(x)) . (x . (W diag(g))^T), so with the norm weight g folded into W once at load, a
@@ -724,112 +724,52 @@ __global__ void __launch_bounds__(256, 1) gemm4w_kernel(Params p) {
       }
     }
 
-    // ---- epilogue: per wave 128 rows x CW bf16 columns through LDS, then 16 B stores
-    bf16_t* ot = reinterpret_cast<bf16_t*>(smem) + wid * 128 * CW;
-    constexpr int CPR_ = CW / 8;
-    constexpr int kIt_ = 128 * CPR_ / 64;                                   // residual chunks per lane
-    constexpr int kGrp_ = kIt_ % 16 == 0 ? 16 : (kIt_ % 12 == 0 ? 12 : 8);  // whole groups only
-    // residual: the first group's loads go out before the accumulators are staged (into registers the main
-    // loop's fragments held), so their HBM round trip overlaps the staging instead of following it
-    uint4v rv0[EPI == EPI_RESIDUAL ? kGrp_ : 1];
-    const int erow0 = __builtin_amdgcn_readfirstlane(m0 + wm * 128);  // uniform: buffer resources in SGPRs
-    const int encol0 = EPI == EPI_SWIGLU ? n0 / 2 + wn * 8 * NT : n0 + wn * 16 * NT;
-    // (a valid pointer and an empty range for the epilogues without a residual operand)
-    const __amdgpu_buffer_rsrc_t rRes =
-        EPI == EPI_RESIDUAL ? uniform_rsrc(p.R + (size_t)erow0 * p.ldc, max(0, min(p.M - erow0, 128)) * p.ldc * 2)
-                            : uniform_rsrc(p.A, 0);
-    if constexpr (EPI == EPI_RESIDUAL) {
-#pragma unroll
-      for (int u = 0; u < kGrp_; ++u) {
-        const int c = lane + 64 * u;
-        const int row = c / CPR_, gn = encol0 + (c % CPR_) * 8;
-        rv0[u] = __builtin_bit_cast(uint4v, __builtin_amdgcn_raw_buffer_load_b128(rRes, (row * p.ldc + gn) * 2, 0, 0));
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float4v t[NT];
-#pragma unroll
-      for (int jj = 0; jj < NT; ++jj) t[jj] = acc[i][jj];
-      if constexpr (RS == 1) {
-        const float4v sc = *reinterpret_cast<const float4v*>(smem + RSV + (wm * 128 + i * 16 + 4 * q) * 4);
-#pragma unroll
-        for (int jj = 0; jj < NT; ++jj) t[jj] *= sc;
-      }
-      if constexpr (EPI == EPI_SWIGLU) {
-        // n-tiles of the wave: W rows wn*128 + jj*16; 32-row blocks alternate gate / up, so gate tiles
-        // {0,1,4,5} pair with up tiles {2,3,6,7}
-#pragma unroll
-        for (int h = 0; h < NT / 4; ++h)
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) t[h * 4 + jj][e] = silu(t[h * 4 + jj][e]) * t[h * 4 + jj + 2][e];
-      }
-      if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
-        // bias re-read per m-tile (L1 hits): loaded once before the K loop it would pin NT VGPRs through it
-        int bcol = n0 + wn * 16 * NT + r16;
-        asm volatile("" : "+v"(bcol));
-#pragma unroll
-        for (int jj = 0; jj < NT; ++jj) {
-          const int col = bcol + jj * 16;
-          const float bv = col < p.N ? bf2f(p.R[col]) : 0.f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float y = t[jj][e] + bv;
-            t[jj][e] = EPI == EPI_BIAS_GELU ? gelu_erf(y) : y;
-          }
-        }
-      }
-#pragma unroll
-      for (int jj = 0; jj < NT; ++jj) {
-        if constexpr (EPI == EPI_SWIGLU) {
-          if ((jj & 3) >= 2) continue;
-        }
-        const int oc = EPI == EPI_SWIGLU ? (jj >> 2) * 32 + (jj & 1) * 16 : jj * 16;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = i * 16 + 4 * q + e, col = oc + r16;
-          ot[row * CW + swz<CW>(row, col)] = f2bf(t[jj][e]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);  // one m-tile's values live at a time
-    }
-    __syncthreads();
-    constexpr int CPR = CW / 8;  // 16 B chunks per row
+    // ---- epilogue: per wave 128 rows x CW columns through LDS, then 16 B stores
+    constexpr int CPR = CW / 8;  // 8-column chunks per row
     const int ncol0 = EPI == EPI_SWIGLU ? n0 / 2 + wn * 8 * NT : n0 + wn * 16 * NT;
     const int ncols = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
     if constexpr (EPI == EPI_RESIDUAL) {
-      // Residual loads branch-free through a buffer resource over this wave's rows (rows past M read zeros
-      // without a request; columns past N are never stored), kGrp of them in flight per lane before the
-      // first add: loaded inside the store's bounds branch, every chunk waited its own HBM round trip
-      // (vmcnt(0) per 16 B, the epilogue's whole latency).
-      const int row0 = erow0;
-      const __amdgpu_buffer_rsrc_t rR = rRes;
-      constexpr int kIt = kIt_;                                   // chunks per lane: 32 (bn 256), 24 (bn 192)
-      constexpr int kGrp = kGrp_;
-      static_assert(kIt % kGrp == 0, "residual epilogue groups must tile the wave's chunks");
-#pragma unroll 1
-      for (int g0 = 0; g0 < kIt; g0 += kGrp) {
-        uint4v rv[kGrp];
-        if (g0 == 0) {
+      // Residual: C = bf16(acc + R) with the add on the fp32 accumulator, one rounding, as the wave-local
+      // epilogue does (adding R to the staged bf16 product rounded twice).  The fp32 image of a wave's 128 x CW
+      // slice is twice its LDS share, so it goes in two halves of 64 rows (m-tiles 0-3, then 4-7): 32 B chunks
+      // under the bf16 image's chunk swizzle.  Residual loads branch-free through a buffer resource over this
+      // wave's rows (rows past M read zeros without a request; columns past N are never stored), a half's
+      // CPR loads per lane all in flight before its accumulators are staged.
+      float* of = reinterpret_cast<float*>(smem) + wid * 64 * CW;
+      const int row0 = __builtin_amdgcn_readfirstlane(m0 + wm * 128);  // uniform: buffer resource in SGPRs
+      const __amdgpu_buffer_rsrc_t rR =
+          uniform_rsrc(p.R + (size_t)row0 * p.ldc, max(0, min(p.M - row0, 128)) * p.ldc * 2);
 #pragma unroll
-          for (int u = 0; u < kGrp; ++u) rv[u] = rv0[u];
-        } else {
+      for (int h = 0; h < 2; ++h) {
+        uint4v rv[CPR];  // 64 rows x CPR chunks over 64 lanes
 #pragma unroll
-          for (int u = 0; u < kGrp; ++u) {
-            const int c = lane + 64 * (g0 + u);
-            const int row = c / CPR, gn = ncol0 + (c % CPR) * 8;
-            rv[u] = __builtin_bit_cast(uint4v, __builtin_amdgcn_raw_buffer_load_b128(rR, (row * p.ldc + gn) * 2, 0, 0));
-          }
+        for (int u = 0; u < CPR; ++u) {
+          const int c = lane + 64 * u;
+          const int row = 64 * h + c / CPR, gn = ncol0 + (c % CPR) * 8;
+          rv[u] = __builtin_bit_cast(uint4v, __builtin_amdgcn_raw_buffer_load_b128(rR, (row * p.ldc + gn) * 2, 0, 0));
         }
 #pragma unroll
-        for (int u = 0; u < kGrp; ++u) {
-          const int c = lane + 64 * (g0 + u);
-          const int row = c / CPR, cch = c % CPR;
-          const int gm = row0 + row, gn = ncol0 + cch * 8;
-          float x[8], y[8];
-          unpack8(*reinterpret_cast<const uint4v*>(ot + row * CW + swz<CW>(row, cch * 8)), x);
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+          for (int jj = 0; jj < NT; ++jj) {
+            const float4v t = acc[4 * h + i][jj];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int row = i * 16 + 4 * q + e, col = jj * 16 + r16;
+              of[row * CW + swz<CW>(row, col)] = t[e];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);  // one m-tile's values live at a time
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < CPR; ++u) {
+          const int c = lane + 64 * u;
+          const int lrow = c / CPR, cch = c % CPR;
+          const int gm = row0 + 64 * h + lrow, gn = ncol0 + cch * 8;
+          const float4v* src = reinterpret_cast<const float4v*>(of + lrow * CW + swz<CW>(lrow, cch * 8));
+          const float4v x0 = src[0], x1 = src[1];
+          float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, y[8];
           unpack8(rv[u], y);
 #pragma unroll
           for (int e = 0; e < 8; ++e) x[e] += y[e];
@@ -848,11 +788,63 @@ __global__ void __launch_bounds__(256, 1) gemm4w_kernel(Params p) {
             sq += __shfl_xor(sq, 4);
             sq += __shfl_xor(sq, 2);
             sq += __shfl_xor(sq, 1);
-            if ((lane & 15) == 0) reinterpret_cast<float*>(smem + RSOFF)[wid * 128 + row] = sq;
+            if ((lane & 15) == 0) reinterpret_cast<float*>(smem + RSOFF)[wid * 128 + 64 * h + lrow] = sq;
           }
         }
+        if (h == 0) __syncthreads();  // the image is read: the second half overwrites it
       }
     } else {
+      bf16_t* ot = reinterpret_cast<bf16_t*>(smem) + wid * 128 * CW;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float4v t[NT];
+#pragma unroll
+        for (int jj = 0; jj < NT; ++jj) t[jj] = acc[i][jj];
+        if constexpr (RS == 1) {
+          const float4v sc = *reinterpret_cast<const float4v*>(smem + RSV + (wm * 128 + i * 16 + 4 * q) * 4);
+#pragma unroll
+          for (int jj = 0; jj < NT; ++jj) t[jj] *= sc;
+        }
+        if constexpr (EPI == EPI_SWIGLU) {
+          // n-tiles of the wave: W rows wn*128 + jj*16; 32-row blocks alternate gate / up, so gate tiles
+          // {0,1,4,5} pair with up tiles {2,3,6,7}
+#pragma unroll
+          for (int h = 0; h < NT / 4; ++h)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) t[h * 4 + jj][e] = silu(t[h * 4 + jj][e]) * t[h * 4 + jj + 2][e];
+        }
+        if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
+          // bias re-read per m-tile (L1 hits): loaded once before the K loop it would pin NT VGPRs through it
+          int bcol = n0 + wn * 16 * NT + r16;
+          asm volatile("" : "+v"(bcol));
+#pragma unroll
+          for (int jj = 0; jj < NT; ++jj) {
+            const int col = bcol + jj * 16;
+            const float bv = col < p.N ? bf2f(p.R[col]) : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float y = t[jj][e] + bv;
+              t[jj][e] = EPI == EPI_BIAS_GELU ? gelu_erf(y) : y;
+            }
+          }
+        }
+#pragma unroll
+        for (int jj = 0; jj < NT; ++jj) {
+          if constexpr (EPI == EPI_SWIGLU) {
+            if ((jj & 3) >= 2) continue;
+          }
+          const int oc = EPI == EPI_SWIGLU ? (jj >> 2) * 32 + (jj & 1) * 16 : jj * 16;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int row = i * 16 + 4 * q + e, col = oc + r16;
+            ot[row * CW + swz<CW>(row, col)] = f2bf(t[jj][e]);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // one m-tile's values live at a time
+      }
+      __syncthreads();
 #pragma unroll 4
       for (int c = lane; c < 128 * CPR; c += 64) {
         const int row = c / CPR, cch = c % CPR;

@@ -337,52 +337,66 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(Params p) {
           }
       }
     }
-    bf16_t* ot = reinterpret_cast<bf16_t*>(smem) + wid * 128 * CW;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = i * 16 + 4 * q + r, col = jj * 16 + r16;
-          ot[row * CW + (col ^ (((row & 7) << 3) % CW))] = f2bf(acc[i][jj][r]);
-        }
-    __syncthreads();
-    constexpr int CPR = CW / 8;    // 16 B chunks per row
+    constexpr int CPR = CW / 8;    // 8-column chunks per row
     constexpr int RPI = 64 / CPR;  // rows per store instruction
     const int cch = lane % CPR;
     const int ncol0 = EPI == EPI_SWIGLU ? n0 / 2 + wc * 32 : n0 + wc * 64;
     const int ncols = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
     if constexpr (EPI == EPI_RESIDUAL) {
-      // residual rows through a buffer resource (rows past M read zeros, no request), all of a group's loads
-      // in flight before the first add — inside the store's bounds branch each 16 B load waited its own
-      // HBM round trip
+      // Residual: C = bf16(acc + R) with the add on the fp32 accumulator, one rounding (adding R to the staged
+      // bf16 product rounded twice).  The fp32 image of a wave's 128 x 64 slice is twice its LDS share, so it
+      // goes in two halves of 64 rows (m-tiles 0-3, then 4-7): 32 B chunks, the same XOR swizzle by chunks.
+      // Residual rows come through a buffer resource (rows past M read zeros, no request), a half's loads all
+      // in flight before the staging.
+      float* of = reinterpret_cast<float*>(smem) + wid * 64 * CW;
       const int row0 = m0 + wr * 128;
       const int rows_here = max(0, min(p.M - row0, 128));
       const __amdgpu_buffer_rsrc_t rR = uniform_rsrc(p.R + (size_t)row0 * p.ldc, rows_here * p.ldc * 2);
       const int gn = ncol0 + cch * 8;
-      constexpr int kIt = 128 / RPI, kGrp = kIt < 16 ? kIt : 16;
-      static_assert(kIt % kGrp == 0, "residual epilogue groups must tile the wave's rows");
-#pragma unroll 1
-      for (int k0 = 0; k0 < kIt; k0 += kGrp) {
-        uint4v rv[kGrp];
+      constexpr int kIt = 64 / RPI;
 #pragma unroll
-        for (int u = 0; u < kGrp; ++u) {
-          const int row = lane / CPR + RPI * (k0 + u);
+      for (int h = 0; h < 2; ++h) {
+        uint4v rv[kIt];
+#pragma unroll
+        for (int u = 0; u < kIt; ++u) {
+          const int row = 64 * h + lane / CPR + RPI * u;
           rv[u] = __builtin_bit_cast(uint4v, __builtin_amdgcn_raw_buffer_load_b128(rR, (row * p.ldc + gn) * 2, 0, 0));
         }
 #pragma unroll
-        for (int u = 0; u < kGrp; ++u) {
-          const int row = lane / CPR + RPI * (k0 + u);
-          float x[8], y[8];
-          unpack8(*reinterpret_cast<const uint4v*>(ot + row * CW + ((cch * 8) ^ (((row & 7) << 3) % CW))), x);
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = i * 16 + 4 * q + r, col = jj * 16 + r16;
+              of[row * CW + (col ^ ((row & 7) << 3))] = acc[4 * h + i][jj][r];
+            }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kIt; ++u) {
+          const int lrow = lane / CPR + RPI * u, row = 64 * h + lrow;
+          const float4v* src = reinterpret_cast<const float4v*>(of + lrow * CW + ((cch * 8) ^ ((lrow & 7) << 3)));
+          const float4v x0 = src[0], x1 = src[1];
+          float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, y[8];
           unpack8(rv[u], y);
 #pragma unroll
           for (int e = 0; e < 8; ++e) x[e] += y[e];
           if (row0 + row < p.M && gn < ncols) *reinterpret_cast<uint4v*>(p.C + (size_t)(row0 + row) * p.ldc + gn) = pack8(x);
         }
+        if (h == 0) __syncthreads();  // the image is read: the second half overwrites it
       }
     } else {
+      bf16_t* ot = reinterpret_cast<bf16_t*>(smem) + wid * 128 * CW;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = i * 16 + 4 * q + r, col = jj * 16 + r16;
+            ot[row * CW + (col ^ (((row & 7) << 3) % CW))] = f2bf(acc[i][jj][r]);
+          }
+      __syncthreads();
 #pragma unroll 4
       for (int k = 0; k < 128 / RPI; ++k) {
         const int row = lane / CPR + RPI * k;
