@@ -34,6 +34,8 @@ int lwc_rms_rowsumsq(const void*, float*, int, int, hipStream_t);
 int lwc_skinny_gemm(const void*, const void*, void*, const void*, int, int, int, int, int, int, hipStream_t);
 int lwc_mxfp4_dequant(const void*, const void*, void*, long long, long long, hipStream_t);
 int lwc_skinny_mxfp4(const void*, const void*, const void*, void*, int, int, int, int, int, int, hipStream_t);
+int lwc_gemm_mxfp4_a8(const void*, const float*, const void*, const void*, void*, int, int, int, int, int, int,
+                      hipStream_t);
 int lwc_lora_shrink(const void*, const void*, const int*, void*, int, int, int, int, int, hipStream_t);
 int lwc_lora_expand_add(void*, const void*, const void*, const int*, int, int, int, int, int, hipStream_t);
 int lwc_gemm8g_fp8(const void*, const void*, void*, const int*, const int*, const float*, const float*, int, int, int,
@@ -589,6 +591,40 @@ void skinny_mxfp4(const at::Tensor& A, const at::Tensor& q, const at::Tensor& s,
            "skinny_mxfp4");
 }
 
+// W4A8 GEMM over an MXFP4 weight (mxfp4_a8.hip): C = (Aq . W^T) * a_scale[row] (epi 0) or the SwiGLU of a 32-row
+// gate/up interleaved W (epi 2, C [M, N / 2]); Aq e4m3 rows, any M
+void gemm_mxfp4_a8(const at::Tensor& A, const at::Tensor& a_scale, const at::Tensor& q, const at::Tensor& s,
+                   at::Tensor& C, int64_t epi) {
+  TORCH_CHECK(epi == 0 || epi == 2, "gemm_mxfp4_a8: epi 0 (plain) or 2 (SwiGLU)");
+  mxfp4_check_weight(q, s, "gemm_mxfp4_a8");
+  CHECK_GPU(A); CHECK_BF16(C);
+  TORCH_CHECK(A.scalar_type() == at::kFloat8_e4m3fn, "gemm_mxfp4_a8: A must be float8_e4m3fn, got ", A.scalar_type());
+  TORCH_CHECK(A.dim() == 2 && A.stride(1) == 1 && C.dim() == 2 && C.stride(1) == 1,
+              "gemm_mxfp4_a8: 2-D row-major A / C");
+  const int64_t M = A.size(0), K = A.size(1), N = q.size(0);
+  const int64_t NC = epi == 2 ? N / 2 : N;
+  TORCH_CHECK(2 * q.size(1) == K && C.size(0) == M && C.size(1) == NC, "gemm_mxfp4_a8: shape mismatch (A [", M, ", ",
+              K, "], W [", N, ", ", 2 * q.size(1), "], C [", C.size(0), ", ", C.size(1), "])");
+  CHECK_GPU(a_scale); CHECK_DTYPE(a_scale, at::kFloat); CHECK_CONTIG(a_scale);
+  TORCH_CHECK(a_scale.numel() == M, "gemm_mxfp4_a8: a_scale must hold one scale per row of A (", M, "), got ",
+              a_scale.numel());
+  TORCH_CHECK(K > 0 && K % 128 == 0 && N % (epi == 2 ? 64 : 16) == 0,
+              "gemm_mxfp4_a8: needs K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0); got K = ", K, ", N = ", N);
+  TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31) && A.stride(0) < (1LL << 31) &&
+                  C.stride(0) < (1LL << 31),
+              "gemm_mxfp4_a8: M, N, K and the row strides must be below 2^31");
+  TORCH_CHECK(M <= 1 || (A.stride(0) % 16 == 0 && A.stride(0) >= K && C.stride(0) >= NC),
+              "gemm_mxfp4_a8: rows of A must be 16-byte aligned, rows of A / C must not overlap");
+  TORCH_CHECK((uintptr_t)A.data_ptr() % 16 == 0 && (uintptr_t)q.data_ptr() % 16 == 0 &&
+                  (uintptr_t)s.data_ptr() % 4 == 0,
+              "gemm_mxfp4_a8: A and the weight's codes must be 16-byte aligned, its scales 4-byte aligned");
+  // (a single row's stride is arbitrary in torch: hand the kernel one that passes its own checks)
+  const int64_t lda = M <= 1 ? K : A.stride(0), ldc = M <= 1 ? NC : C.stride(0);
+  CHECK_RC(lwc_gemm_mxfp4_a8(A.data_ptr(), a_scale.data_ptr<float>(), q.data_ptr(), s.data_ptr(), C.data_ptr(), (int)M,
+                             (int)N, (int)K, (int)lda, (int)ldc, (int)epi, cur_stream()),
+           "gemm_mxfp4_a8");
+}
+
 // batched LoRA (lora.hip): T[m] = X[m] . A[ids[m]]^T, then Y[m] += T[m] . B[ids[m]]^T; ids outside
 // [0, n_adapters) (-1) mean no adapter: the row of T is not written, the row of Y not touched
 void lora_check_ids(const at::Tensor& ids, int64_t M, const char* who) {
@@ -1092,6 +1128,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm", &skinny_gemm);
   m.def("mxfp4_dequant", &mxfp4_dequant);
   m.def("skinny_mxfp4", &skinny_mxfp4);
+  m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand_add", &lora_expand_add);
   m.def("rms_rowsumsq", &rms_rowsumsq);

@@ -724,7 +724,8 @@ def _tp_num_blocks(model, dev, kv_fraction: float) -> int:
 def build_engine(spec: dict, wid: int):
     """Default worker factory: a decoder engine on ``spec['device']`` from a server model spec
     ({"arch", "weights": "random:<seed>" | path, "max_model_len", "max_batch", "kv_fraction", "fp8",
-    "mxfp4": MXFP4 weight-only projections (ops/mxfp4.py), "prefix_caching", "chunked_prefill", "constrained_logprobs", "tokenizer": path to a tokenizer.json,
+    "mxfp4": MXFP4 weight-only projections (ops/mxfp4.py), "mxfp4_act": "bf16" | "e4m3" their activation format,
+    "prefix_caching", "chunked_prefill", "constrained_logprobs", "tokenizer": path to a tokenizer.json,
     "adapters": {name: adapter spec} — LoRA adapters served as "<model>:<name>", models/lora.py}); MoE archs get
     the Mixtral model."""
     import torch
@@ -771,7 +772,8 @@ def build_engine(spec: dict, wid: int):
     else:
         lora = load_adapters(cfg, spec["adapters"]) if adapters else None  # (the model lays them out, once)
         model = LlamaModel(cfg, device=dev, seed=seed, weights_path=path, max_position=mlen + 64,
-                           fp8_dense=bool(spec.get("fp8", False)), lora=lora, mxfp4=bool(spec.get("mxfp4", False)))
+                           fp8_dense=bool(spec.get("fp8", False)), lora=lora, mxfp4=bool(spec.get("mxfp4", False)),
+                           mxfp4_act=spec.get("mxfp4_act"))
     tok = load_tokenizer(spec, cfg.vocab_size, cfg.bos_token_id, cfg.eos_token_id)
     return LLMEngine(model, tok, max_batch=int(spec.get("max_batch", 512)), max_model_len=mlen,
                      kv_memory_fraction=kv_fraction, num_blocks=num_blocks,

@@ -65,16 +65,26 @@ def check_decoder(cfg: DecoderConfig) -> None:
                          "head_dim 128 only")
 
 
+# activation formats of the MXFP4 projections: "bf16" (weight-only) or "e4m3" (W4A8 from ops.MXFP4_A8_MIN_ROWS rows)
+MXFP4_ACTS = ("bf16", "e4m3")
+
+
 def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool = False, mxfp4: bool = False,
                   adapters: bool = False, embedder: bool = False, device_type: Optional[str] = None,
-                  who: str = "") -> None:
+                  who: str = "", mxfp4_act: Optional[str] = None) -> None:
     """Refuse the decoder variants that do not combine (the model constructors, ``lora.check_model_spec`` and
     the embedding service all call this with the facts they know; ``cfg`` None: an arch not registered).
 
     MXFP4 weight-only projections (ops/mxfp4.py) and LoRA adapters (models/lora.py) each run on the dense
     single-GPU generation decoder only, not with fp8 weights and not with each other; the adapters on the GPU
-    kernels only (``device_type``, where the caller has a device).  ``who`` prefixes the message."""
+    kernels only (``device_type``, where the caller has a device).  ``who`` prefixes the message.
+
+    ``mxfp4_act`` (None: not given): the activation format of the MXFP4 projections, one of ``MXFP4_ACTS`` and only
+    together with mxfp4 weights; whatever mxfp4 weights refuse is refused first, in the same words."""
     moe = cfg is not None and bool(cfg.num_experts)
+    if mxfp4_act is not None and not mxfp4:
+        why = "\"mxfp4_act\" needs \"mxfp4\": true" if who else "mxfp4_act needs mxfp4=True"
+        raise ValueError(f"{who}: {why}" if who else why)
     for on, what in ((mxfp4, "mxfp4 weights"), (adapters, "LoRA adapters")):
         if not on:
             continue
@@ -94,6 +104,9 @@ def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool =
             why = "LoRA adapters run on the GPU kernels only"
         if why is not None:
             raise ValueError(f"{who}: {why}" if who else why)
+    if mxfp4_act is not None and mxfp4_act not in MXFP4_ACTS:
+        why = f"mxfp4_act {mxfp4_act!r}: must be one of {', '.join(repr(a) for a in MXFP4_ACTS)}"
+        raise ValueError(f"{who}: {why}" if who else why)
 
 
 @dataclass(frozen=True)

@@ -128,25 +128,36 @@ class LlamaModel:
     # the residual stream itself; the tensor-parallel and MoE subclasses reduce / route them first (False there)
     single_rank_dense = True
     tp_size = 1
+    # the activation format of the MXFP4 projections ("e4m3": ``mxfp4_act``, below); a class-level default, so an
+    # object that states only its facts (no constructor run) is the bf16-activation model
+    act_format = "bf16"
 
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8_dense: bool = False,
-                 fold_norms: bool = True, lora=None, mxfp4: bool = False):
+                 fold_norms: bool = True, lora=None, mxfp4: bool = False, mxfp4_act: Optional[str] = None):
         check_decoder(cfg)  # shapes the kernels do not serve are refused here, by arch name
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         check_variant(cfg, tp=self.tp_size > 1, fp8=fp8_dense, mxfp4=mxfp4, adapters=lora is not None,
-                      device_type=self.device.type)
+                      device_type=self.device.type, mxfp4_act=mxfp4_act)
         # The variant, stated once; everything below reads these (and the class's ``single_rank_dense``).
         # "mxfp4" (ops/mxfp4.py): qkv / o / gate|up / down as 4-bit codes with one e8m0 scale per 32, bf16
         # activations; on a CPU device the model holds the dequantised bf16 weights (the same function, through
         # F.linear).  "fp8" (BASELINE config 5): the same projections (a MoE decoder's: attention and experts) in
         # e4m3 with per-channel scales, activations quantised per row; lm_head stays bf16.  The dense decoder's
         # fp8 exists on the GPU only: on a CPU device it stays "bf16"
+        # ``mxfp4_act="e4m3"`` (with "mxfp4"; default "bf16": the weight-only model, bit for bit): every GEMM call
+        # of at least ops.MXFP4_A8_MIN_ROWS rows runs row-quantised e4m3 activations x the packed weight on the
+        # block-scaled MFMA (ops.gemm_mxfp4_a8: no dequantisation, no scratch); calls with fewer rows are the
+        # weight-only path unchanged.  Routed by the call's row count alone, never by a timing.  Like the dense
+        # fp8 flag it exists on the GPU only: a CPU model accepts it and computes with bf16 activations on the
+        # dequantised weights (``act_format`` stays "bf16")
         self.moe = bool(cfg.num_experts)
         self.on_gpu = self.device.type == "cuda"
         self.weight_format = "mxfp4" if mxfp4 else "fp8" if fp8_dense and (self.on_gpu or self.moe) else "bf16"
         if self.moe and self.single_rank_dense:
             raise NotImplementedError("MoE decoders use models.mixtral.MixtralModel")
+        if mxfp4 and mxfp4_act == "e4m3" and self.on_gpu:
+            self.act_format = "e4m3"
         self.mx_scratch: Optional[torch.Tensor] = None  # bf16, the largest projection (ops.linear_mxfp4)
         self.cos, self.sin = rope_tables(cfg, self.device, max_position)
         if weights_path:
@@ -155,7 +166,7 @@ class LlamaModel:
             self._random_init(seed)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
         self.g8_ws = None
-        if self.mxfp4 and self.on_gpu:
+        if self.mxfp4 and self.on_gpu and not self._mx_no_scratch():
             # one dequantisation buffer for every projection past 64 rows, allocated here: never inside a capture
             n = max(math.prod(w.shape) for L in self.layers for w in (L.wqkv, L.wo, L.w_gate_up, L.w_down))
             self.mx_scratch = torch.empty(n, dtype=torch.bfloat16, device=self.device)
@@ -485,6 +496,14 @@ class LlamaModel:
         projections: the norm also emits the per-row e4m3 activation (ops.QAct) in the same pass, so no separate
         quantisation kernel re-reads the normalised rows (the MLP's with its bf16 rows where ``_mlp_reads_bf16``);
         "out" — the bf16 lm_head / pooling, and every norm of the other weight formats: the bf16 kernel."""
+        if self.act_format == "e4m3" and feeds != "out":
+            # MXFP4 with e4m3 activations: from the W4A8 row threshold on, the consumer (qkv / gate|up) takes the
+            # row-quantised activation; below it, the bf16 rows of the weight-only path
+            L0 = self.layers[0]
+            a8 = self._a8(x.shape[0], L0.wqkv) if feeds == "attn" else \
+                self._a8(x.shape[0], L0.w_gate_up, swiglu=L0.gu_block == 32)
+            if a8:
+                return ops.rmsnorm_quant_fp8(x, w, self.cfg.rms_eps, **kw)
         if self.weight_format != "fp8" or feeds == "out":
             return ops.rmsnorm(x, w, self.cfg.rms_eps, **kw)
         if feeds == "mlp":
@@ -523,6 +542,27 @@ class LlamaModel:
         return (os.environ.get("LWC_ATTN_MX", "1") != "0" and self.weight_format == "fp8"
                 and self.cfg.head_dim == 128 and ops.FP8_GEMM != "blas" and self.layers[0].wo.q.shape[0] % 8 == 0)
 
+    def _a8(self, M: int, w, swiglu: bool = False) -> bool:
+        """Whether a GEMM call of ``M`` rows over the MXFP4 weight ``w`` runs e4m3 activations on the block-scaled
+        MFMA: the model's ``act_format``, the row threshold and the kernel's shape predicate — nothing timed."""
+        if self.act_format != "e4m3" or M < ops.MXFP4_A8_MIN_ROWS or not isinstance(w, Mxfp4Weight):
+            return False
+        return ops.mxfp4_a8_ok(M, w.shape[0], w.shape[1], swiglu=swiglu)
+
+    def _mx_no_scratch(self) -> bool:
+        """Whether no call can reach the dequantise-into-scratch path: every projection of every layer is taken by
+        skinny_mxfp4 below ops.MXFP4_A8_MIN_ROWS rows and by the W4A8 kernel from there on."""
+        if self.act_format != "e4m3":
+            return False
+        lo, hi = ops.MXFP4_A8_MIN_ROWS - 1, ops.MXFP4_A8_MIN_ROWS
+
+        def both(w, swiglu=False):
+            N, K = w.shape
+            return all(ops.skinny_mxfp4_ok(m, N, K, swiglu) for m in (1, lo)) and self._a8(hi, w, swiglu)
+
+        return all(both(L.wqkv) and both(L.wo) and both(L.w_down) and L.gu_block == 32 and both(L.w_gate_up, True)
+                   for L in self.layers)
+
     # the constructor's flags, as the engine and the tests read them
     fp8_dense = property(lambda self: self.weight_format == "fp8" and not self.moe)
     mxfp4 = property(lambda self: self.weight_format == "mxfp4")
@@ -538,7 +578,12 @@ class LlamaModel:
         fp8 GEMM (gemm8g dense or the library, ops.linear_fp8_q)."""
         if isinstance(w, ops.Fp8Weight):
             return ops.linear_fp8(x, w)
-        if isinstance(w, Mxfp4Weight):  # M <= 64: the MXFP4 weight stream; above: dequantise + the bf16 path
+        if isinstance(w, Mxfp4Weight):
+            if isinstance(x, ops.QAct) or self._a8(x.shape[0], w):  # e4m3 activations x the packed weight
+                return ops.linear_mxfp4_a8(x, w)
+            if self.mx_scratch is None:  # (_mx_no_scratch: every call below the W4A8 threshold is the weight stream)
+                return ops.skinny_mxfp4(x.contiguous(), w)
+            # M <= 64: the MXFP4 weight stream; above: dequantise + the bf16 path
             return ops.linear_mxfp4(x, w, self.mx_scratch, ws=self.g8_ws)
         if not self.on_gpu:
             return F.linear(x, w)
@@ -564,6 +609,10 @@ class LlamaModel:
     def _act(self, h: torch.Tensor, L) -> torch.Tensor:
         """silu(h Wg^T) * (h Wu^T): the gate|up GEMM with its SwiGLU."""
         if isinstance(L.w_gate_up, Mxfp4Weight):
+            if isinstance(h, ops.QAct):  # (_norm emitted it: this call runs W4A8)
+                return ops.swiglu_mxfp4_a8(h, L.w_gate_up, L.gu_block)
+            if self.mx_scratch is None:
+                return ops.skinny_mxfp4(h.contiguous(), L.w_gate_up, swiglu=True)
             return ops.swiglu_mxfp4(h, L.w_gate_up, L.gu_block, self.mx_scratch, ws=self.g8_ws)
         if not self.on_gpu:
             return ops.silu_mul(F.linear(h, L.w_gate_up), block=L.gu_block)

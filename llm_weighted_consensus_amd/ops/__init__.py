@@ -542,6 +542,51 @@ def swiglu_mxfp4(x: torch.Tensor, w: Mxfp4Weight, block: int, scratch: torch.Ten
     return gemm_plan.swiglu(x, _mxfp4_scratch(w, scratch), block, ws=ws)
 
 
+# W4A8: e4m3 activations x the packed MXFP4 weight on the block-scaled MFMA (csrc/kernels/mxfp4_a8.hip).  A model
+# built with ``mxfp4_act="e4m3"`` takes it from this many rows of a GEMM call on; below, the weight-only path
+MXFP4_A8_MIN_ROWS = 65
+
+
+def mxfp4_a8_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
+    return M >= 1 and K > 0 and K % 128 == 0 and N % (64 if swiglu else 16) == 0
+
+
+def gemm_mxfp4_a8(xq: torch.Tensor, xs: torch.Tensor, w: Mxfp4Weight, out: Optional[torch.Tensor] = None,
+                  swiglu: bool = False) -> torch.Tensor:
+    """(e4m3 rows ``xq`` [M, K], row scales ``xs`` [M]) . W^T for an MXFP4 weight, the weight read as stored (no
+    dequantisation, no scratch): bf16 [M, N] = ``xs[m] * sum_k xq[m, k] * dequant(W)[n, k]``, fp32 accumulation, one
+    bf16 rounding; ``swiglu``: W's rows gate|up interleaved in blocks of 32, output silu(gate) * up [M, N / 2].
+    Any M >= 1; rows of ``xq`` 16-byte aligned (may be a strided view).  Needs K % 128 == 0 and N % 16 == 0
+    (SwiGLU: N % 64 == 0) (:func:`mxfp4_a8_ok`); other shapes are refused.  One launch at any size: the kernel
+    addresses its operands with 64-bit pointers, so nothing is split into row blocks."""
+    if out is None:
+        out = torch.empty(xq.shape[0], w.shape[0] // 2 if swiglu else w.shape[0], dtype=torch.bfloat16,
+                          device=xq.device)
+    kernels().gemm_mxfp4_a8(xq, xs.reshape(-1), w.q, w.s, out, 2 if swiglu else 0)
+    return out
+
+
+def _a8_rows(x):
+    return (x.q, x.s) if isinstance(x, QAct) else quant_fp8_rows(x)
+
+
+def linear_mxfp4_a8(x, w: Mxfp4Weight) -> torch.Tensor:
+    """x [M, K] . W^T for an MXFP4 weight with e4m3 activations: ``x`` is bf16 rows (quantised per row here,
+    :func:`quant_fp8_rows`) or a :class:`QAct` from the producing norm; then :func:`gemm_mxfp4_a8`."""
+    xq, xs = _a8_rows(x)
+    return gemm_mxfp4_a8(xq, xs, w)
+
+
+def swiglu_mxfp4_a8(x, w: Mxfp4Weight, block: int) -> torch.Tensor:
+    """silu(x Wg^T) * (x Wu^T) [M, F] bf16 for an MXFP4 gate|up weight interleaved in blocks of ``block`` (32: the
+    kernel's SwiGLU epilogue; otherwise the plain GEMM and one silu_mul pass), activations as
+    :func:`linear_mxfp4_a8`."""
+    xq, xs = _a8_rows(x)
+    if block == 32:
+        return gemm_mxfp4_a8(xq, xs, w, swiglu=True)
+    return silu_mul(gemm_mxfp4_a8(xq, xs, w), block=block)
+
+
 def gemm4w(A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, swiglu: bool = False, bias: Optional[torch.Tensor] = None,
            gelu: bool = False, bn: int = 256, chain: "Optional[NormChain]" = None, var: int = 0,

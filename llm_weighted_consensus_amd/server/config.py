@@ -21,6 +21,11 @@ variables configure the local engine:
                     checkpoint is quantised at load, one written by scripts/quantize_mxfp4.py is taken as it
                     is.  Dense Llama-family models only: refused with "fp8", "tp" > 1, "adapters", MoE archs
                     and in LWC_EMBED_MODELS
+                    "mxfp4_act": "e4m3" (with "mxfp4": true; default "bf16") runs every projection call of at
+                    least 65 rows — prefill, mixed steps, decode batches past 64 — with per-row e4m3
+                    activations on the block-scaled MFMA, reading the packed weight directly (no
+                    dequantisation pass, no scratch buffer; csrc/kernels/mxfp4_a8.hip); smaller calls stay
+                    the bf16-activation weight stream.  Refused without "mxfp4": true and for any other value
   LWC_EMBED_MODELS  JSON {name: {"arch": "bge-large-en-v1.5", "weights": "random:<seed>" | <path>}}
   LWC_GPU           device index for this process's engine (one process per GPU)
   LWC_GPUS          comma list of devices: serve each model through an EngineGroup (one worker process

@@ -605,6 +605,150 @@ def skinny_ab(dev):
             del x, ws, acc
 
 
+def _rand_mx(dev, N, K):  # timing only: any codes, scales near 2^-6
+    from llm_weighted_consensus_amd import ops
+
+    q = torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8)
+    s = torch.randint(117, 125, (N, K // 32), device=dev, dtype=torch.uint8)
+    return ops.Mxfp4Weight.from_packed(q, s)
+
+
+def _rotating(items):
+    it = [0]
+
+    def nxt():
+        it[0] = (it[0] + 1) % len(items)
+        return items[it[0]]
+    return nxt
+
+
+def _graph_medians(runs, iters, rounds=7):
+    """us per call: each arm captured as one graph of ``iters`` calls (the serving decode step is a captured
+    graph: eager launches of kernels this short time the host, not the device), replays interleaved."""
+    graphs = {}
+    for k, fn in runs.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        graphs[k] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[k]):
+            for _ in range(iters):
+                fn()
+        graphs[k].replay()
+    torch.cuda.synchronize()
+    t = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, g in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            g.replay()
+            e.record()
+            e.synchronize()
+            t[k].append(s.elapsed_time(e) / iters * 1e3)
+    return {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+
+
+def _decode_step_ms(model, cfg, dev, B):
+    """Median ms of one captured decode step of B rows at position 32 (23 replays, the first 3 dropped)."""
+    from llm_weighted_consensus_amd.models.llama import KVCache
+
+    i32 = dict(dtype=torch.int32, device=dev)
+    pos = 32
+    cache = KVCache(cfg, 3 * B, 16, dev)
+    bt = torch.arange(3 * B, **i32).view(B, 3)
+    positions, ctx = torch.full((B,), pos, **i32), torch.full((B,), pos + 1, **i32)
+    slots = (bt[:, 2] * 16).contiguous()
+    tokens = torch.randint(0, cfg.vocab_size, (B,), device=dev).int()
+    model.tune_gemms(B)
+
+    def fwd():
+        return model.decode(tokens, positions, slots, bt, ctx, cache, num_splits=1)
+
+    for _ in range(2):
+        fwd()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fwd()
+    ts = []
+    for _ in range(23):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        g.replay()
+        e.record()
+        e.synchronize()
+        ts.append(s.elapsed_time(e))
+    ts = sorted(ts[3:])
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def mxfp4a8_ab(dev):
+    """MXFP4 weights with e4m3 activations (ops.gemm_mxfp4_a8, profiles/mxfp4_a8.md) at the Llama-3-8B shapes, arms
+    interleaved in one process, median of 7 rounds, weights rotated over more copies than the last-level cache holds:
+    (a) per projection and M in {33, 48, 64, 128, 512, 2048, 4096} (MX_M overrides): the W4A8 kernel — for o and
+        down with the activation's quant_fp8_rows pass, which no norm fuses (the kernel alone is printed too); qkv
+        and gate|up read the fused norm's QAct —, the parent path ops.linear_mxfp4 / swiglu_mxfp4 (weight stream up
+        to 64 rows, dequantise + the planner's bf16 GEMM above), the planner's bf16 GEMM on a bf16 weight, and
+        gemm8g_dense on an Fp8Weight of the same shape;
+    (b) one llama-3-8b random-weight decode step (captured graph) at B in {128, 4096} (MX_B overrides):
+        bf16 / mxfp4 / mxfp4 + e4m3.
+    MX_PARTS=a,b selects the parts."""
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.llama import LlamaModel
+    from llm_weighted_consensus_amd.ops import gemm_plan
+
+    parts = os.environ.get("MX_PARTS", "a,b").split(",")
+    shapes = [("qkv", 6144, 4096, False, True), ("o", 4096, 4096, False, False),
+              ("gate_up", 28672, 4096, True, True), ("down", 4096, 14336, False, False)]  # (.., swiglu, norm-fused)
+    Ms = [int(m) for m in os.environ.get("MX_M", "33,48,64,128,512,2048,4096").split(",")]
+    for name, N, K, sw, fused in shapes if "a" in parts else []:
+        nw = max(2, min(16, (768 << 20) // (N * K * 2)))
+        wb = _rotating([((torch.rand(N, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16) for _ in range(nw)])
+        w8 = _rotating([ops.Fp8Weight(wb()) for _ in range(2 * nw)])
+        wm = _rotating([_rand_mx(dev, N, K) for _ in range(4 * nw)])
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device=dev)
+        for M in Ms:
+            x = (torch.rand(M, K, device=dev) * 2 - 1).to(torch.bfloat16)
+            xq, xs = ops.quant_fp8_rows(x)
+            gemm_plan.tune(x, wb(), "swiglu" if sw else "plain", 32 if sw else 0)  # parent and bf16 arms run its choice
+            runs = {"a8 kernel": lambda: ops.gemm_mxfp4_a8(xq, xs, wm(), swiglu=sw),
+                    "fp8": lambda: ops.gemm8g_dense(xq, xs, w8(), swiglu=sw)}
+            if not fused:
+                runs["a8"] = lambda: ops.linear_mxfp4_a8(x, wm())
+            if sw:
+                runs["parent"] = lambda: ops.swiglu_mxfp4(x, wm(), 32, scratch)
+                runs["bf16"] = lambda: gemm_plan.swiglu(x, wb(), 32)
+            else:
+                runs["parent"] = lambda: ops.linear_mxfp4(x, wm(), scratch)
+                runs["bf16"] = lambda: gemm_plan.linear(x, wb())
+            t = _graph_medians(runs, 20 if M <= 128 else 6 if M <= 512 else 3)
+            a8 = t["a8 kernel" if fused else "a8"]
+            tf = 2.0 * M * N * K / a8 / 1e6
+            print(f"mxfp4a8 (a) {name} {N}x{K} M={M}: a8 {a8:8.1f} us ({tf:6.0f} TF/s"
+                  f"{'' if fused else ', kernel alone %.1f us' % t['a8 kernel']})  parent {t['parent']:8.1f} us  "
+                  f"bf16[{gemm_plan.choice(M, N, K, 'swiglu' if sw else 'plain')}] {t['bf16']:8.1f} us  "
+                  f"fp8 g8g {t['fp8']:8.1f} us  a8/parent {a8 / t['parent']:.2f}x"
+                  f"{'  SLOWER than parent' if a8 > t['parent'] else ''}", flush=True)
+        del wb, w8, wm, scratch
+        torch.cuda.empty_cache()
+    if "b" not in parts:
+        return
+    cfg = decoder_config("llama-3-8b")
+    for label, kw in (("bf16", {}), ("mxfp4", {"mxfp4": True}), ("mxfp4+e4m3", {"mxfp4": True, "mxfp4_act": "e4m3"})):
+        torch.cuda.empty_cache()
+        model = LlamaModel(cfg, device=dev, seed=0, max_position=256, **kw)
+        torch.cuda.synchronize()
+        print(f"mxfp4a8 (b) llama-3-8b [{label}]: {torch.cuda.memory_allocated(dev) / 2 ** 30:.1f} GiB allocated, "
+              f"scratch {0 if model.mx_scratch is None else model.mx_scratch.nbytes >> 20} MiB", flush=True)
+        for B in [int(b) for b in os.environ.get("MX_B", "128,4096").split(",")]:
+            med, lo, hi = _decode_step_ms(model, cfg, dev, B)
+            print(f"mxfp4a8 (b) llama-3-8b [{label}] decode step B={B}: median {med:.3f} ms (min {lo:.3f}, "
+                  f"max {hi:.3f})", flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
 def mxfp4_ab(dev):
     """MXFP4 weight-only projections at the Llama-3-8B shapes (profiles/mxfp4.md), arms interleaved in one
     process, median of 7 rounds, weights rotated over more copies than the last-level cache holds:
@@ -623,50 +767,12 @@ def mxfp4_ab(dev):
     shapes = [("qkv", 6144, 4096, False), ("o", 4096, 4096, False), ("gate_up", 28672, 4096, True),
               ("down", 4096, 14336, False)]
 
-    def rand_mx(N, K):  # timing only: any codes, scales near 2^-6
-        q = torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8)
-        s = torch.randint(117, 125, (N, K // 32), device=dev, dtype=torch.uint8)
-        return ops.Mxfp4Weight.from_packed(q, s)
-
-    def rotating(items):
-        it = [0]
-
-        def nxt():
-            it[0] = (it[0] + 1) % len(items)
-            return items[it[0]]
-        return nxt
-
-    def med(runs, iters):
-        """us per call: each arm captured as one graph of ``iters`` calls (the serving decode step is a captured
-        graph: eager launches of kernels this short time the host, not the device), replays interleaved."""
-        graphs = {}
-        for k, fn in runs.items():
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            graphs[k] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graphs[k]):
-                for _ in range(iters):
-                    fn()
-            graphs[k].replay()
-        torch.cuda.synchronize()
-        t = {k: [] for k in runs}
-        for _ in range(7):
-            for k, g in graphs.items():
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                g.replay()
-                e.record()
-                e.synchronize()
-                t[k].append(s.elapsed_time(e) / iters * 1e3)
-        return {k: sorted(v)[len(v) // 2] for k, v in t.items()}
-
     for name, N, K, sw in shapes:
         if not ({"a", "b"} & set(parts)):
             break
         nw = max(2, min(16, (768 << 20) // (N * K * 2)))
-        wb = rotating([((torch.rand(N, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16) for _ in range(nw)])
-        wm = rotating([rand_mx(N, K) for _ in range(4 * nw)])  # (a quarter of the bytes each)
+        wb = _rotating([((torch.rand(N, K, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16) for _ in range(nw)])
+        wm = _rotating([_rand_mx(dev, N, K) for _ in range(4 * nw)])  # (a quarter of the bytes each)
         scratch = torch.empty(N * K, dtype=torch.bfloat16, device=dev)
         mxb, bfb = N * K * (0.5 + 1 / 32), N * K * 2.0
         for M in ([int(m) for m in os.environ.get("MX_M", "1,8,16,32,64").split(",")] if "a" in parts else []):
@@ -679,7 +785,7 @@ def mxfp4_ab(dev):
             else:
                 runs = {"mxfp4": lambda: ops.skinny_mxfp4(x, wm()), "gv": lambda: ops.skinny_gemm(x, wb()),
                         "planner": lambda: gemm_plan.linear(x, wb())}
-            t = med(runs, 20)
+            t = _graph_medians(runs, 20)
             ch = gemm_plan.choice(M, N, K, "swiglu" if sw else "plain")
             print(f"mxfp4 (a) {name} {N}x{K} M={M}: mxfp4 {t['mxfp4']:7.1f} us ({mxb / t['mxfp4'] / 1e3:6.0f} GB/s)  "
                   f"gv {t['gv']:7.1f} us ({bfb / t['gv'] / 1e3:6.0f} GB/s)  planner[{ch}] {t['planner']:7.1f} us "
@@ -693,7 +799,7 @@ def mxfp4_ab(dev):
             else:
                 runs = {"dq+gemm": lambda: ops.linear_mxfp4(x, wm(), scratch), "gemm": lambda: gemm_plan.linear(x, wb())}
             runs["dq"] = lambda: ops.mxfp4_dequant(wm(), scratch.view(N, K))
-            t = med(runs, 10)
+            t = _graph_medians(runs, 10)
             print(f"mxfp4 (b) {name} {N}x{K} M={M}: dequant+gemm {t['dq+gemm']:7.1f} us  gemm {t['gemm']:7.1f} us  "
                   f"dequant alone {t['dq']:6.1f} us ({(mxb + bfb) / t['dq'] / 1e3:5.0f} GB/s read+written)  "
                   f"+{(t['dq+gemm'] / t['gemm'] - 1) * 100:.0f} %", flush=True)
@@ -1157,6 +1263,8 @@ def main():
         skinny_ab(dev)
     if "mxfp4" in a.what:
         mxfp4_ab(dev)
+    if "mxfp4a8" in a.what:
+        mxfp4a8_ab(dev)
     if "lora" in a.what:
         lora_kernels(dev)
     if "lorastep" in a.what:
