@@ -179,20 +179,24 @@ void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const c10::opti
                    const at::Tensor& cos_t, const at::Tensor& sin_t, at::Tensor& k_cache, at::Tensor& v_cache,
                    int64_t Hq, int64_t Hkv, int64_t D, bool rope_q) {
   CHECK_BF16(qkv); CHECK_CONTIG(qkv);
-  CHECK_GPU(positions); CHECK_DTYPE(positions, at::kInt);
+  CHECK_GPU(positions); CHECK_DTYPE(positions, at::kInt); CHECK_CONTIG(positions);
+  CHECK_GPU(cos_t); CHECK_GPU(sin_t); CHECK_CONTIG(cos_t); CHECK_CONTIG(sin_t);
   CHECK_DTYPE(cos_t, at::kFloat); CHECK_DTYPE(sin_t, at::kFloat);
-  CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+  CHECK_BF16(k_cache); CHECK_BF16(v_cache); CHECK_CONTIG(k_cache);
+  TORCH_CHECK(Hq > 0 && Hkv > 0 && D > 0 && D % 16 == 0, "rope_kv_write: needs Hq, Hkv >= 1 and head_dim % 16 == 0");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (Hq + 2 * Hkv) * D, "rope_kv_write: qkv row is not (Hq+2Hkv)*D");
   const int T = (int)qkv.size(0);
-  TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D, "rope_kv_write: qkv row is not (Hq+2Hkv)*D");
   TORCH_CHECK(positions.numel() == T, "rope_kv_write: positions length");
-  TORCH_CHECK(cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2, "rope_kv_write: cos/sin table width");
+  TORCH_CHECK(cos_t.dim() == 2 && sin_t.dim() == 2 && cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2 &&
+                  cos_t.size(0) == sin_t.size(0),
+              "rope_kv_write: cos/sin table shape");
   // k_cache [NB, Hkv, BS, D]; v_cache [NB, Hkv, BS/4, D, 4] (4-token interleaved)
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == D, "rope_kv_write: k_cache shape");
   check_v_cache(v_cache, k_cache, "rope_kv_write");
   const int BS = (int)k_cache.size(2);
   const int* sp = nullptr;
   if (slots.has_value() && slots->defined()) {
-    CHECK_DTYPE(*slots, at::kInt);
+    CHECK_GPU(*slots); CHECK_DTYPE(*slots, at::kInt); CHECK_CONTIG(*slots);
     TORCH_CHECK(slots->numel() == T, "rope_kv_write: slots length");
     sp = slots->data_ptr<int>();
   }

@@ -22,6 +22,18 @@ def _close(a, b, atol, rtol=0.0):
     assert (err <= lim).all(), f"max err {err.max().item():.4g} (atol {atol}, rtol {rtol})"
 
 
+# The norm, SwiGLU, embedding and RoPE tests below draw N(0, 1) inputs and accept 2e-2 .. 4e-2 + 1 .. 2 %: many
+# bf16 steps at |y| ~ 1.  They cover shapes and the dispatch between kernels, but an RMSNorm that leaves one
+# element of a 4096-wide row out of its sum of squares, counts it twice or divides by d - 8 stays within one
+# bf16 code of the truth and passes; so do a truncating store, a norm taken from the unrounded x + r and a sigmoid
+# that went through bf16.  RoPE + KV write runs at one shape, and its cache writes are checked by counting
+# non-zeros in zero-filled caches.  tests/test_rowwise_probes_gpu.py runs the same entry points (and the fp8
+# row quantisers, kv_gather, kv_block_copy) on structured inputs against fp64 oracles: spike walks over every
+# 16-byte slot, eps / residual / pinned rows, exact rotation tables, sentinel-filled caches and caged outputs;
+# tests/test_rowwise_probes.py shows what those comparisons reject.  A change to one of these kernels wants both
+# files green.
+
+
 @pytest.mark.parametrize("d,rows", [(384, 37), (1024, 37), (4096, 37), (2048, 301), (4096, 258), (8192, 256)])
 @pytest.mark.parametrize("with_res", [False, True])
 def test_rmsnorm(gpu, d, rows, with_res):
