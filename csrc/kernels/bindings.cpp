@@ -847,7 +847,9 @@ void ep_combine(const at::Tensor& ret, const at::Tensor& row_off, const at::Tens
 
 void moe_combine(const at::Tensor& Y, const at::Tensor& inv, const at::Tensor& w, int64_t k, at::Tensor& out) {
   CHECK_BF16(Y); CHECK_BF16(out); CHECK_CONTIG(Y); CHECK_CONTIG(out);
+  CHECK_GPU(inv); CHECK_GPU(w); CHECK_CONTIG(inv); CHECK_CONTIG(w);  // the kernel indexes both as flat [T * k]
   CHECK_DTYPE(inv, at::kInt); CHECK_DTYPE(w, at::kFloat);
+  TORCH_CHECK(Y.dim() == 2 && out.dim() == 2 && k >= 1, "moe_combine: Y [rows, d], out [T, d], k >= 1");
   const int T = (int)out.size(0), d = (int)out.size(1);
   TORCH_CHECK(Y.size(1) == d && inv.numel() >= (int64_t)T * k && w.numel() >= (int64_t)T * k, "moe_combine: shapes");
   CHECK_RC(lwc_moe_combine(Y.data_ptr(), inv.data_ptr<int>(), w.data_ptr<float>(), T, (int)k, d, out.data_ptr(),
@@ -999,11 +1001,14 @@ void pool_l2norm(const at::Tensor& hidden, const at::Tensor& cu_seqlens, int64_t
                  const c10::optional<at::Tensor>& out_bf16) {
   CHECK_BF16(hidden); CHECK_DTYPE(cu_seqlens, at::kInt); CHECK_DTYPE(out_f32, at::kFloat);
   TORCH_CHECK(hidden.dim() == 2 && hidden.stride(1) == 1, "pool_l2norm: hidden must be [T, d]");
+  // the kernel reads cu[s] and writes out[s * d + c] through flat pointers
+  CHECK_GPU(cu_seqlens); CHECK_CONTIG(cu_seqlens); CHECK_GPU(out_f32); CHECK_CONTIG(out_f32);
+  TORCH_CHECK(cu_seqlens.numel() >= 1, "pool_l2norm: cu_seqlens must hold nseq + 1 offsets");
   const int nseq = (int)cu_seqlens.numel() - 1, d = (int)hidden.size(1);
   TORCH_CHECK(out_f32.numel() == (int64_t)nseq * d, "pool_l2norm: out shape");
   void* ob = nullptr;
   if (out_bf16.has_value() && out_bf16->defined()) {
-    CHECK_BF16(*out_bf16);
+    CHECK_BF16(*out_bf16); CHECK_CONTIG(*out_bf16);
     TORCH_CHECK(out_bf16->numel() == (int64_t)nseq * d, "pool_l2norm: bf16 out shape");
     ob = out_bf16->data_ptr();
   }
@@ -1054,6 +1059,10 @@ void cosine_consensus(const at::Tensor& E, at::Tensor& S, double inv_tau, at::Te
   TORCH_CHECK(E.dim() == 3, "cosine_consensus: E must be [R, n, d]");
   const int R = (int)E.size(0), n = (int)E.size(1), d = (int)E.size(2);
   const int n_pad = (n + 15) / 16 * 16;
+  for (const at::Tensor* t : {&S, &centrality, &weights, &best}) {  // written through flat pointers
+    CHECK_GPU(*t); CHECK_CONTIG(*t);
+  }
+  CHECK_DTYPE(centrality, at::kFloat); CHECK_DTYPE(weights, at::kFloat); CHECK_DTYPE(best, at::kInt);
   TORCH_CHECK(S.scalar_type() == at::kFloat && S.numel() >= (int64_t)R * n_pad * n_pad, "cosine_consensus: S size");
   TORCH_CHECK(centrality.numel() >= (int64_t)R * n && weights.numel() >= (int64_t)R * n && best.numel() >= R,
               "cosine_consensus: outputs too small");

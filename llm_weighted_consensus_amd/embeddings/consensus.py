@@ -42,11 +42,15 @@ class ConsensusResult:
 
 
 def consensus_reference(E: torch.Tensor, tau: float) -> ConsensusResult:
-    """fp32 torch form of K10a (CPU plumbing path and the numerics oracle)."""
+    """fp32 torch form of K10a (CPU plumbing path and the numerics oracle).  A sole candidate (n = 1: a shard
+    of one after a lost all-gather) has no peers to agree with; like the kernel it gets centrality 1, weight 1."""
     Ef = E.float()
     S = Ef @ Ef.transpose(1, 2)
     n = E.shape[1]
-    cen = (S.sum(-1) - S.diagonal(dim1=1, dim2=2)) / max(1, n - 1)
+    if n == 1:
+        cen = torch.ones(E.shape[0], 1, dtype=torch.float32, device=E.device)
+    else:
+        cen = (S.sum(-1) - S.diagonal(dim1=1, dim2=2)) / (n - 1)
     w = torch.softmax(cen / tau, -1)
     return ConsensusResult(cen.argmax(-1).tolist(), w, cen, S)
 

@@ -168,7 +168,8 @@ class ConsensusClient:
             cen, w = cen[0].tolist(), w[0].tolist()
         else:  # CPU plumbing path (tests / no GPU): same math in torch
             Sm = E @ E.t()
-            cen_t = (Sm.sum(1) - Sm.diagonal()) / max(1, n - 1)
+            # a sole candidate: centrality 1, as the kernel and consensus_reference give it
+            cen_t = (Sm.sum(1) - Sm.diagonal()) / (n - 1) if n > 1 else torch.ones(1, dtype=Sm.dtype)
             cen, w = cen_t.tolist(), torch.softmax(cen_t / tau, 0).tolist()
         created = int(time.time())
         usage = comp.usage.clone() if comp.usage else C.Usage()

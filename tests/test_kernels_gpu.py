@@ -675,6 +675,7 @@ def test_sample_skip_logprob(gpu):
         _close(lp1, lsm.gather(1, t1.long()[:, None])[:, 0], 2e-3, 1e-3)
 
 
+# pool_l2norm, cosine_consensus, knn_topk, moe_route / moe_router / moe_combine: exact probes in tests/test_select_probes_gpu.py
 def test_pool_cosine(gpu):
     from llm_weighted_consensus_amd import ops
 

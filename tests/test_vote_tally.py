@@ -140,6 +140,7 @@ def test_make_batcher_spec():
     assert b.min_batch == 4 and b.device == "cuda:0"
 
 
+# C = 1024, a request without a valid voter and R = 0: tests/test_select_probes_gpu.py::test_vote_tally_edges
 @pytest.mark.gpu
 def test_vote_tally_kernel_bitwise(gpu):
     rng = random.Random(2)
