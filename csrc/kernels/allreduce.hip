@@ -38,6 +38,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace ar {

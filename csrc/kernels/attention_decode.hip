@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

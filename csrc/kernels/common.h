@@ -98,11 +98,6 @@ LWC_DEVICE float row_sum4(float v) {
   return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
 
-
-// A buffer resource built from explicitly wave-uniform parts (readfirstlane of the base address and the
-// size).  Built straight from kernel arguments / tile indices, the compiler sometimes cannot prove the
-// resource uniform and wraps EVERY buffer access through it in a readfirstlane "waterfall" loop (~10
-// instructions and a branch per access, inside GEMM main loops too).
 // e8m0 exponent of an MX block with max |x| = amax: the smallest e with amax * 2^-e <= 448 (e4m3's largest
 // finite), from amax's own exponent and mantissa (448 = 0.875 * 2^9), so no rounding pushes a value past 448
 LWC_DEVICE int mx_exp(float amax) {
@@ -119,6 +114,10 @@ LWC_DEVICE float row16_max(float x) {
   return fmaxf(x, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x140, 0xF, 0xF, false)));
 }
 
+// A buffer resource built from explicitly wave-uniform parts (readfirstlane of the base address and the
+// size).  Built straight from kernel arguments / tile indices, the compiler sometimes cannot prove the
+// resource uniform and wraps EVERY buffer access through it in a readfirstlane "waterfall" loop (~10
+// instructions and a branch per access, inside GEMM main loops too).
 LWC_DEVICE __amdgpu_buffer_rsrc_t uniform_rsrc(const void* base, int bytes) {
   const uint64_t a = (uint64_t)base;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);

@@ -13,6 +13,7 @@
 //                              stays on the host (a launch costs more than the arithmetic); the serving
 //                              path batches the tallies of concurrent requests (score/tally_batch.py).
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

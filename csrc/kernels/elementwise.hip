@@ -7,6 +7,7 @@
 // All of them move 16 B per lane (Guideline 13); trig comes from a host-built cos/sin table
 // (Appendix B "Element-wise": on-device sin/cos turns RoPE VALU-bound).
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

@@ -26,6 +26,7 @@
 // Six launches besides the GEMMs (pack, exchange, unpack, back, exchange, combine) where the torch glue
 // they replace issued ~20 index / scatter / searchsorted kernels per layer.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

@@ -15,6 +15,7 @@
 // Both operands are K-contiguous (torch.nn.functional.linear layout), so A and W tiles share one
 // staging / fragment code path.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

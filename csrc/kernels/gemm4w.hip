@@ -65,6 +65,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace g4w {

@@ -24,6 +24,7 @@
 // weight tile of an expert is read from HBM once per XCD and reused from its L2 by the expert's other
 // m-tiles.  Surplus slots (routing decides the m-tile count at run time) exit immediately.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace g8g {

@@ -50,6 +50,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace g8p {

@@ -27,6 +27,7 @@
 // expand-add: a workgroup owns 64 rows; each wave keeps the T fragments of the 4 row tiles in registers and
 // walks 16-column tiles of Y, reading the adapter's B rows of that tile (16 x R) once for the 64 rows.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace lora {

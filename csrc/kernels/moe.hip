@@ -12,6 +12,7 @@
 //   quant_fp8_rows : per-row dynamic e4m3 (OCP) quantisation: scale = amax / 448.
 // The expert GEMMs themselves are the grouped MFMA GEMM (gemm.hip) reading A through src_row.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

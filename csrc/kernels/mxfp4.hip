@@ -20,6 +20,7 @@
 //
 // Requires K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0), M <= 64, lda % 4 == 0, ldc % 4 == 0.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace mxfp4 {

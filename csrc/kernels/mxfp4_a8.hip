@@ -36,6 +36,7 @@
 // only a grid past 2^31 - 1 workgroups is refused.
 // Requires K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0), lda % 16 == 0, lda >= K.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace mxa8 {

@@ -9,6 +9,7 @@
 // src/score/llm/mod.rs:10) and the embeddings encoder (`WeightTrainingTableEmbeddings.model`,
 // src/score/model/mod.rs:309-314).
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

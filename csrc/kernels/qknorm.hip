@@ -9,6 +9,7 @@
 // the first unit are multiples of 8, the block size a multiple of 64), so the lanes of a group are always
 // active together.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

@@ -17,6 +17,7 @@
 // top_logprobs <= 20 (:455-467) feeding the vote extractor (src/score/completions/client.rs:1721-1793),
 // and constrained output modes (json_schema / tool_call, src/score/llm/mod.rs:690-696).
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 

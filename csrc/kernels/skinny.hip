@@ -21,6 +21,7 @@
 // Requires K % 2048 == 0 (8 waves x an even number of 4-step batches of 32), N % 16 == 0, M <= 64, lda / ldc % 4 == 0; the
 // planner (ops/gemm_plan.py, backend "gv") times it against hipBLASLt per decode bucket.
 #include "common.h"
+#include "launchers.h"
 
 namespace lwc {
 namespace skinny {

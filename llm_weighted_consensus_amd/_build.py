@@ -87,7 +87,7 @@ def build_kernels(jobs: int = 8, force: bool = False) -> Path:
     bsrc = kdir / "bindings.cpp"
     bobj = obj_dir / "bindings.o"
     objs.append(bobj)
-    if force or _stale(bobj, [bsrc]):
+    if force or _stale(bobj, [bsrc, *headers]):
         jobs_list.append(["hipcc", "-O2", "-fPIC", "-std=c++17", "-x", "c++", "-I/opt/rocm/include", *tflags, "-c", str(bsrc), "-o", str(bobj)])
     with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
         for f in [ex.submit(_run, c) for c in jobs_list]:

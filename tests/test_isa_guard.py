@@ -70,7 +70,7 @@ def test_round5_tail_reshape_is_caught(tmp_path):
     between the MFMAs, and the guard must report them."""
     _built_object()
     kdir = ROOT / "csrc" / "kernels"
-    for f in ("gemm4w.hip", "common.h"):
+    for f in ("gemm4w.hip", "common.h", "launchers.h"):
         shutil.copy(kdir / f, tmp_path / f)
     src = (tmp_path / "gemm4w.hip").read_text()
     old = """      for (; r + 2 < nt; ++r) G4_TILE_H(r, 1, true)
