@@ -674,6 +674,33 @@ void moe_router(const at::Tensor& h, const at::Tensor& router, int64_t k, at::Te
            who);
 }
 
+// moe_wide.hip: 16 < E <= 128, k <= 8 (the launchers refuse the rest); h rows and router rows are read 16 B at a time
+void moe_route_wide(const at::Tensor& logits, int64_t k, at::Tensor& topk_ids, at::Tensor& topk_w,
+                    at::Tensor& row_off, at::Tensor& src_row, at::Tensor& inv) {
+  const char* who = "moe_route_wide";
+  const void* lp = flat(logits, BF16, who, "logits");
+  TORCH_CHECK(logits.dim() == 2 && k >= 1, who, ": logits must be [T, E], k >= 1");
+  const int T = (int)logits.size(0), E = (int)logits.size(1);
+  const RouteOutputs o = route_outputs(topk_ids, topk_w, row_off, src_row, inv, T, k, E, who);
+  CHECK_RC(lwc_moe_route_wide(lp, T, E, (int)k, o.topk_ids, o.topk_w, o.row_off, o.src_row, o.inv, cur_stream()),
+           who);
+}
+
+void moe_router_wide(const at::Tensor& h, const at::Tensor& router, int64_t k, at::Tensor& topk_ids,
+                     at::Tensor& topk_w, at::Tensor& row_off, at::Tensor& src_row, at::Tensor& inv,
+                     const OptTensor& logits) {
+  const char* who = "moe_router_wide";
+  const Strided hs = strided(h, BF16, who, "h", 8);
+  const void* rp = flat(router, BF16, who, "router");
+  TORCH_CHECK(router.dim() == 2 && h.size(1) == router.size(1) && k >= 1, who, ": h [T, d], router [E, d], k >= 1");
+  TORCH_CHECK(h.size(0) <= 1 || hs.ld >= h.size(1), who, ": h rows overlap (row stride ", hs.ld, " < d)");
+  const int T = (int)h.size(0), E = (int)router.size(0), d = (int)h.size(1);
+  const RouteOutputs o = route_outputs(topk_ids, topk_w, row_off, src_row, inv, T, k, E, who);
+  CHECK_RC(lwc_moe_router_wide(hs.p, hs.ld, rp, T, E, d, (int)k, o.topk_ids, o.topk_w, o.row_off, o.src_row, o.inv,
+                               opt_flat(logits, BF16, who, "logits", exactly((int64_t)T * E)), cur_stream()),
+           who);
+}
+
 void moe_combine(const at::Tensor& Y, const at::Tensor& inv, const at::Tensor& w, int64_t k, at::Tensor& out) {
   const char* who = "moe_combine";
   const void* yp = flat(Y, BF16, who, "Y");
@@ -1018,6 +1045,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm8p_slots", &lwc_gemm8p_slots);
   m.def("moe_route", &moe_route);
   m.def("moe_router", &moe_router);
+  m.def("moe_route_wide", &moe_route_wide);
+  m.def("moe_router_wide", &moe_router_wide);
   m.def("moe_combine", &moe_combine);
   m.def("quant_fp8_rows", &quant_fp8_rows);
   m.def("paged_decode_cascade", &paged_decode_cascade);

@@ -97,6 +97,14 @@ int lwc_moe_router(const void* h, int ldh, const void* router, int T, int E, int
 int lwc_moe_combine(const void* Y, const int* inv, const float* w, int T, int k, int d, void* out, hipStream_t s);
 int lwc_quant_fp8_rows(const void* x, int rows, int d, void* q, float* scale, hipStream_t s);
 
+// ---- moe_wide.hip: the same outputs for 16 < E <= 128, 1 <= k <= 8; anything else is refused (-1)
+int lwc_moe_route_wide(const void* logits, int T, int E, int k, int* topk_ids, float* topk_w, int* row_off,
+                       int* src_row, int* inv, hipStream_t s);
+int lwc_moe_router_wide(const void* h, int ldh, const void* router, int T, int E, int d, int k, int* topk_ids,
+                        float* topk_w, int* row_off, int* src_row, int* inv, void* logits, hipStream_t s);
+int lwc_moe_permute_wide(const int* topk_ids, int T, int E, int k, int* row_off, int* src_row, int* inv,
+                         hipStream_t s);
+
 // ---- ep.hip: send / recv [W, (C + 1) * RB] bytes; row_bytes / out_bytes: one row of x in bytes
 int lwc_ep_pack(const void* x, const float* xs, const int* src, const int* row_off, int W, int El, int C, int RB,
                 int row_bytes, void* send, hipStream_t s);

@@ -727,7 +727,7 @@ def build_engine(spec: dict, wid: int):
     "mxfp4": MXFP4 weight-only projections (ops/mxfp4.py), "mxfp4_act": "bf16" | "e4m3" their activation format,
     "prefix_caching", "chunked_prefill", "constrained_logprobs", "tokenizer": path to a tokenizer.json,
     "adapters": {name: adapter spec} — LoRA adapters served as "<model>:<name>", models/lora.py}); MoE archs get
-    the Mixtral model."""
+    the Mixtral model, those with ``qk_norm`` the Qwen3-MoE one."""
     import torch
 
     from ..models.config import decoder_config
@@ -749,6 +749,7 @@ def build_engine(spec: dict, wid: int):
     num_blocks = None
     if cfg.num_experts:
         from ..models.mixtral import MixtralModel
+        from ..models.qwen_moe import Qwen3MoeModel
 
         tp_kw = {}
         if tp > 1:
@@ -756,8 +757,9 @@ def build_engine(spec: dict, wid: int):
             tp_kw = dict(tp_rank=rank, tp_size=tp, tp_comm=comm)
             if spec.get("tp_shared"):
                 kv_fraction /= tp
-        model = MixtralModel(cfg, device=dev, seed=seed, weights_path=path, max_position=mlen + 64,
-                             fp8=bool(spec.get("fp8", False)), **tp_kw)
+        moe_cls = Qwen3MoeModel if cfg.qk_norm else MixtralModel  # (tp > 1 was refused above for Qwen3-MoE)
+        model = moe_cls(cfg, device=dev, seed=seed, weights_path=path, max_position=mlen + 64,
+                        fp8=bool(spec.get("fp8", False)), **tp_kw)
         if tp > 1:
             num_blocks = _tp_num_blocks(model, dev, kv_fraction)
     elif tp > 1:

@@ -104,6 +104,10 @@ def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool =
             why = "LoRA adapters run on the GPU kernels only"
         if why is not None:
             raise ValueError(f"{who}: {why}" if who else why)
+    if moe and cfg.qk_norm and (tp or embedder):
+        # Qwen3-MoE (models/qwen_moe.py): one device, generation only
+        why = f"{cfg.name} {'is served as a generation model only' if embedder else 'runs on one device: no tp > 1'}"
+        raise ValueError(f"{who}: {why}" if who else why)
     if mxfp4_act is not None and mxfp4_act not in MXFP4_ACTS:
         why = f"mxfp4_act {mxfp4_act!r}: must be one of {', '.join(repr(a) for a in MXFP4_ACTS)}"
         raise ValueError(f"{who}: {why}" if who else why)
@@ -191,6 +195,16 @@ DECODERS.update({
                              max_position=2048, eos_token_id=2),
     "qwen3-g5-tiny": replace(_qwen("qwen3-g5-tiny", 4096, 512, 2, 10, 2, 1024, True, qk_norm=True),
                              max_position=2048, eos_token_id=2),
+})
+
+# Qwen3-MoE (models/qwen_moe.py): ``ffn`` is the per-expert moe_intermediate_size; 128 experts, 8 per token, the
+# Qwen3 attention block.  qwen3-30b-a3b is from memory of the public config (see the Llama-3.2 note above).  The
+# tiny arch keeps 128 experts and top-8 (the wide router's shape) at an ffn of 3 x 128, no power of two, as 768.
+DECODERS.update({
+    "qwen3-30b-a3b": replace(_qwen("qwen3-30b-a3b", 151936, 2048, 48, 32, 4, 768, False, qk_norm=True),
+                             max_position=40960, num_experts=128, experts_per_token=8),
+    "qwen3-moe-tiny": replace(_qwen("qwen3-moe-tiny", 4096, 512, 2, 8, 2, 384, False, qk_norm=True),
+                              max_position=2048, eos_token_id=2, num_experts=128, experts_per_token=8),
 })
 
 ENCODERS = {

@@ -57,14 +57,16 @@ class MoELayerWeights:
     s13: Optional[torch.Tensor]   # fp8 per-channel scales [E, 2F_local]
     s2: Optional[torch.Tensor]    # [E, d]
     gu_block: int = 0             # >0: w13 rows interleave gate|up in blocks of this size (fp8 path)
-    # the Qwen attention block's fields (LayerWeights): no MoE decoder has them, the constructor refuses the configs
+    # the Qwen attention block's fields (LayerWeights): no MoE decoder has a q|k|v bias (the constructor refuses
+    # the config); the per-head q / k norm weights [D] are set by models.qwen_moe.Qwen3MoeModel only
     bqkv: None = None
-    q_norm: None = None
-    k_norm: None = None
+    q_norm: Optional[torch.Tensor] = None
+    k_norm: Optional[torch.Tensor] = None
 
 
 class MixtralModel(TensorParallel, LlamaModel):
     single_rank_dense = False
+    qk_norm_attention = False  # a subclass that fills the layers' q_norm / k_norm says so (Qwen3MoeModel)
     fp8 = property(lambda self: self.weight_format == "fp8")  # (LlamaModel states it: ``fp8_dense=fp8``)
 
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
@@ -75,7 +77,7 @@ class MixtralModel(TensorParallel, LlamaModel):
         check_variant(cfg, tp=tp_size > 1, fp8=fp8, mxfp4=mxfp4)
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
-        if cfg.qkv_bias or cfg.qk_norm:
+        if cfg.qkv_bias or (cfg.qk_norm and not self.qk_norm_attention):
             raise NotImplementedError(f"{cfg.name}: the MoE decoder has no q|k|v bias and no q/k head norm")
         if ep_size > 1 and tp_size > 1:
             raise ValueError("choose TP or EP for the MoE decoder, not both")

@@ -785,10 +785,45 @@ def moe_router(h: torch.Tensor, router: torch.Tensor, k: int, want_logits: bool 
     return out + (logits,) if want_logits else out
 
 
+def _route_outputs(T: int, E: int, k: int, dev):
+    return (torch.empty(T, k, dtype=torch.int32, device=dev), torch.empty(T, k, dtype=torch.float32, device=dev),
+            torch.empty(E + 1, dtype=torch.int32, device=dev), torch.empty(T * k, dtype=torch.int32, device=dev),
+            torch.empty(T * k, dtype=torch.int32, device=dev))
+
+
+def moe_route_wide(logits: torch.Tensor, k: int):
+    """:func:`moe_route` for 16 < E <= 128 experts and k <= 8 (csrc/kernels/moe_wide.hip: a token's logits spread
+    over 16 lanes).  The same five tensors, the same contract; any other E is refused."""
+    T, E = logits.shape
+    out = _route_outputs(T, E, k, logits.device)
+    kernels().moe_route_wide(logits.contiguous(), int(k), *out)
+    return out
+
+
+def moe_router_wide(h: torch.Tensor, router: torch.Tensor, k: int, want_logits: bool = False):
+    """:func:`moe_router` for 16 < E <= 128 experts and k <= 8: the router projection on the MFMA fused with the
+    top-k of :func:`moe_route_wide` (the logits are rounded to bf16 first, as ``F.linear`` would hold them).
+    h [T, d] bf16 with unit column stride, d % 8 == 0 and a row stride that is a multiple of 8; router [E, d]
+    contiguous."""
+    T, E = h.shape[0], router.shape[0]
+    out = _route_outputs(T, E, k, h.device)
+    logits = torch.empty(T, E, dtype=torch.bfloat16, device=h.device) if want_logits else None
+    kernels().moe_router_wide(h, router, int(k), *out, logits)
+    return out + (logits,) if want_logits else out
+
+
+ROUTE_WIDE_MIN_EXPERTS = 65  # ops.route: E <= 64 keeps the kernels of moe.hip
+
+
 def route(h: torch.Tensor, router: torch.Tensor, k: int):
     """MoE routing of bf16 rows: the fused router kernel on the GPU (E <= 16, d % 8 == 0), else the
-    router projection + :func:`moe_route`."""
-    if h.is_cuda and router.shape[0] <= 16 and h.shape[1] % 8 == 0 and h.stride(1) == 1 and h.stride(0) % 8 == 0:
+    router projection + :func:`moe_route`.  More than 64 experts take the wide pair in the same way."""
+    fusable = h.is_cuda and h.shape[1] % 8 == 0 and h.stride(1) == 1 and h.stride(0) % 8 == 0
+    if router.shape[0] >= ROUTE_WIDE_MIN_EXPERTS:
+        if fusable:
+            return moe_router_wide(h, router, k)
+        return moe_route_wide(torch.nn.functional.linear(h, router), k)
+    if fusable and router.shape[0] <= 16:
         return moe_router(h, router, k)
     return moe_route(torch.nn.functional.linear(h, router), k)
 

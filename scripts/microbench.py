@@ -1238,6 +1238,93 @@ def qknorm(dev):
         print(f"  one decode layer B={B} [{k}]: {v * 1e3:.1f} us")
 
 
+def qwen_moe(dev):
+    """Qwen3-MoE (profiles/qwen_moe.md): the wide router against a torch composition, one decode step of the
+    qwen3-30b-a3b shapes at 4 layers with its parts, and the whole-model cosines of qwen3-moe-tiny against the fp32
+    oracle of tests/qwen_moe_ref.py.  Arms interleaved in one process, medians of 7 rounds of captured graphs."""
+    import sys
+    from pathlib import Path
+
+    import torch.nn.functional as F
+
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.qwen_moe import Qwen3MoeModel
+
+    out = Path(os.environ.get("QWENMOE_OUT", Path(__file__).resolve().parent.parent / "profiles" / "qwen_moe.md"))
+    d, E, k = 2048, 128, 8
+    lines = ["# Qwen3-MoE: the wide router and one decode step (`python scripts/microbench.py qwenmoe`)", "",
+             f"MI355X, torch {torch.__version__}.  Arms interleaved in one process, median of 7 rounds; every arm is a "
+             "captured graph of 20 calls (a decode step is a captured graph: eager launches this short time the host).",
+             "", "## Router: `moe_router_wide` vs a torch composition (d = 2048, E = 128, k = 8)", "",
+             "torch: `F.linear` -> `topk` -> `softmax` -> stable `argsort` of the flat ids (the dispatch permutation).",
+             "unfused: `F.linear` -> `moe_route_wide` (the library GEMM, then the same top-k and permutation).",
+             "", "| T | moe_router_wide us | unfused us | torch us | wide / torch | wide / unfused |", "|---|---|---|---|---|---|"]
+    router = (torch.randn(E, d, device=dev) * 0.1).to(torch.bfloat16)
+    for T in (1, 64, 512, 4096):
+        h = torch.randn(T, d, device=dev).to(torch.bfloat16)
+
+        def torch_route():
+            top, ids = F.linear(h, router).float().topk(k, dim=-1)
+            return ids, top.softmax(-1), torch.argsort(ids.flatten(), stable=True)
+
+        t = _graph_medians({"wide": lambda: ops.moe_router_wide(h, router, k), "torch": torch_route,
+                            "unfused": lambda: ops.moe_route_wide(F.linear(h, router), k)}, 20)
+        cells = [f"**{r:.2f} (slower)**" if r > 1 else f"{r:.2f}" for r in (t["wide"] / t["torch"], t["wide"] / t["unfused"])]
+        lines.append(f"| {T} | {t['wide']:.1f} | {t['unfused']:.1f} | {t['torch']:.1f} | {cells[0]} | {cells[1]} |")
+        print(lines[-1], flush=True)
+
+    lines += ["", "## One decode step, qwen3-30b-a3b shapes at 4 layers (context 32, captured graph)", "",
+              "route: `ops.route`; expert FFN: row quantisation (fp8), the two grouped GEMMs with the SwiGLU between "
+              "them, `moe_combine`; lm_head: the 151936 x 2048 projection timed alone; the rest (norms, qkv / o "
+              "projections, QK-norm + RoPE + KV write, decode attention, embedding) is the remainder.", "",
+              "| weights | B | step ms | route | expert FFN | lm_head | attention block + rest | expert FFN us / layer "
+              "| expert weight GB/s |", "|---|---|---|---|---|---|---|---|---|"]
+    cfg = decoder_config("qwen3-30b-a3b", layers=4)
+    for fp8 in (False, True):
+        model = Qwen3MoeModel(cfg, device=dev, seed=0, max_position=128, fp8=fp8)
+        L = model.layers[0]
+        wbytes = 3 * cfg.hidden * cfg.ffn * E * (1 if fp8 else 2)
+        for B in (64, 512, 4096):
+            step = _decode_step_ms(model, cfg, dev, B)[0]
+            x = torch.randn(B, cfg.hidden, device=dev).to(torch.bfloat16)
+            t = _graph_medians({"route": lambda: ops.route(x, L.router, k), "mlp": lambda: model._mlp(x, L),
+                                "head": lambda: model._proj(x, model.lm_head)}, 10)
+            ffn = t["mlp"] - t["route"]
+            route_s, ffn_s, head_s = (cfg.layers * t["route"] / 1e3 / step, cfg.layers * ffn / 1e3 / step,
+                                      t["head"] / 1e3 / step)
+            lines.append(f"| {'fp8' if fp8 else 'bf16'} | {B} | {step:.3f} | {route_s:.1%} | {ffn_s:.1%} | {head_s:.1%} | "
+                         f"{1 - route_s - ffn_s - head_s:.1%} | {ffn:.0f} | {wbytes / ffn / 1e3:.0f} |")
+            print(lines[-1], flush=True)
+        del model, L
+        torch.cuda.empty_cache()
+    lines += ["", "At B = 64 a step routes 512 rows to 128 experts: about 4 rows per expert, each in a 128-row tile of "
+              "the grouped GEMM (256 in gemm8g), so 97 % of the MFMA rows are padding while every expert's weights are "
+              "streamed once.  The last column is what that costs: the expert weights of a layer divided by the expert "
+              "FFN time, to hold against the ~5 TB/s a weight-streaming kernel reaches.  The lead, not built here: a "
+              "16- or 32-row tail tile in the grouped GEMM, or a weight-stream (skinny) kernel per expert for "
+              "segments of a few rows."]
+
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    from tests.test_qwen_moe_gpu import _model, _model_cosines
+
+    lines += ["", "## Whole model against the fp32 oracle (qwen3-moe-tiny)", "",
+              "Largest 1 - cos over the prefill's last-token logits (37 tokens) and 7 decode steps; the bounds of "
+              "tests/test_qwen_moe_gpu.py are 1 - 4 x the largest value of a row, within [0.99, Mixtral's bound].", "",
+              "| weights | seed 2 | seed 3 | seed 4 |", "|---|---|---|---|"]
+    for fp8 in (False, True):
+        worst = []
+        for seed in (2, 3, 4):
+            m = _model(dev, fp8, seed)
+            worst.append(1 - min(_model_cosines(m, dev)))
+            del m
+        lines.append(f"| {'fp8' if fp8 else 'bf16'} | " + " | ".join(f"{v:.3g}" for v in worst) + " |")
+        print(lines[-1], flush=True)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["gemm", "attn", "sample", "small"])
@@ -1271,6 +1358,8 @@ def main():
         lora_step(dev)
     if "qknorm" in a.what:
         qknorm(dev)
+    if "qwenmoe" in a.what:
+        qwen_moe(dev)
     if "g48" in a.what:
         g48_ab(dev)
     if "g8ab" in a.what:
