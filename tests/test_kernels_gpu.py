@@ -676,6 +676,7 @@ def test_sample_skip_logprob(gpu):
 
 
 # pool_l2norm, cosine_consensus, knn_topk, moe_route / moe_router / moe_combine: exact probes in tests/test_select_probes_gpu.py
+# ep_pack / ep_unpack / ep_back / ep_combine: tests/test_ep_probes_gpu.py; lora_shrink / lora_expand_add: tests/test_lora_probes_gpu.py
 def test_pool_cosine(gpu):
     from llm_weighted_consensus_amd import ops
 

@@ -59,6 +59,8 @@ def _check(out, Y0, want, mag, ids):
         assert torch.equal(out[none].view(torch.int16), Y0[none].view(torch.int16))
 
 
+# lora_shrink / lora_expand_add: exact probes (every rank 16..192, 64 adapters, every k and r walked, bitwise) in
+# tests/test_lora_probes_gpu.py; tests/test_lora_probes.py shows what those comparisons reject.
 @pytest.mark.parametrize("R", [16, 48, 64])
 @pytest.mark.parametrize("K,N", [(512, 1536), (4096, 520)])
 @pytest.mark.parametrize("M", [1, 17, 300])
