@@ -544,6 +544,38 @@ void gemm_mxfp4_a8(const at::Tensor& A, const at::Tensor& a_scale, const at::Ten
            who);
 }
 
+// grouped skinny GEMM over a stack of MXFP4 expert weights (moe_mxfp4.hip): q [E, N, K / 2], s [E, N, K / 32];
+// rows [row_off[e], row_off[e + 1]) of C are expert e's, computed from A[a_rows[row]] (a_rows given) or A[row]
+void moe_skinny_mxfp4(const at::Tensor& A, const at::Tensor& q, const at::Tensor& s, at::Tensor& C,
+                      const at::Tensor& row_off, const OptTensor& a_rows, int64_t epi) {
+  const char* who = "moe_skinny_mxfp4";
+  TORCH_CHECK(epi == 0 || epi == 2, who, ": epi 0 (plain) or 2 (SwiGLU)");
+  const void *qp = flat(q, U8, who, "q"), *sp = flat(s, U8, who, "s");
+  TORCH_CHECK(q.dim() == 3 && s.dim() == 3 && s.size(0) == q.size(0) && s.size(1) == q.size(1) &&
+                  q.size(2) == 16 * s.size(2),
+              who, ": q must be [E, N, K / 2] and s [E, N, K / 32] with K % 32 == 0");
+  const Strided a = strided(A, BF16, who, "A"), c = strided(C, BF16, who, "C");
+  const int64_t E = q.size(0), N = q.size(1), K = A.size(1), rows = C.size(0);
+  const int64_t NC = epi == 2 ? N / 2 : N;
+  TORCH_CHECK(2 * q.size(2) == K && C.size(1) == NC, who, ": shape mismatch (A [", A.size(0), ", ", K, "], W [", E,
+              ", ", N, ", ", 2 * q.size(2), "], C [", rows, ", ", C.size(1), "])");
+  TORCH_CHECK(K > 0 && K % 128 == 0 && N % (epi == 2 ? 64 : 16) == 0, who,
+              ": needs K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0); got K = ", K, ", N = ", N);
+  TORCH_CHECK(E >= 1 && E <= 65535 && N <= INT_MAX && K <= INT_MAX, who,
+              ": E must be in [1, 65535], N and K below 2^31");
+  TORCH_CHECK(row_off.dim() == 1, who, ": row_off must be 1-D [E + 1]");
+  const int* ro = flat<int>(row_off, I32, who, "row_off", exactly(E + 1));
+  const int* ar = opt_flat<int>(a_rows, I32, who, "a_rows", exactly(rows));
+  TORCH_CHECK(present(a_rows) || A.size(0) >= rows, who, ": without a_rows A must hold C's ", rows, " rows, has ",
+              A.size(0));
+  TORCH_CHECK(a.ld % 4 == 0 && c.ld % 4 == 0 && a.ld >= K && c.ld >= NC && (uintptr_t)a.p % 8 == 0 &&
+                  (uintptr_t)c.p % 8 == 0,
+              who, ": rows of A / C must be 8-byte aligned and not overlap");
+  CHECK_RC(lwc_moe_skinny_mxfp4(a.p, qp, sp, c.p, ro, ar, (int)E, (long long)rows, (long long)A.size(0), (int)N, (int)K,
+                                a.ld, c.ld, (int)epi, cur_stream()),
+           who);
+}
+
 // batched LoRA (lora.hip): T[m] = X[m] . A[ids[m]]^T, then Y[m] += T[m] . B[ids[m]]^T; ids outside
 // [0, n_adapters) (-1) mean no adapter: the row of T is not written, the row of Y not touched
 const int* lora_check_ids(const at::Tensor& ids, int64_t M, const char* who) {
@@ -1039,6 +1071,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mxfp4_dequant", &mxfp4_dequant);
   m.def("skinny_mxfp4", &skinny_mxfp4);
   m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8);
+  m.def("moe_skinny_mxfp4", &moe_skinny_mxfp4);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand_add", &lora_expand_add);
   m.def("rms_rowsumsq", &rms_rowsumsq);

@@ -82,6 +82,12 @@ int lwc_skinny_mxfp4(const void* A, const void* Q, const void* S, void* C, int M
 int lwc_gemm_mxfp4_a8(const void* A, const float* a_scale, const void* Q, const void* S, void* C, int M, int N, int K,
                       int lda, int ldc, int epi, hipStream_t s);
 
+// ---- moe_mxfp4.hip: Q [E, N, K / 2], S [E, N, K / 32]; row_off [E + 1]; a_rows [rows] optional (else A has >= rows
+// rows, expert-major); A has a_nrows rows
+int lwc_moe_skinny_mxfp4(const void* A, const void* Q, const void* S, void* C, const int* row_off, const int* a_rows,
+                         int E, long long rows, long long a_nrows, int N, int K, int lda, int ldc, int epi,
+                         hipStream_t s);
+
 // ---- lora.hip: A [n_adapters, R, K], B [n_adapters, N, R], ids [M]
 int lwc_lora_shrink(const void* X, const void* A, const int* ids, void* T, int M, int K, int R, int ldx,
                     int n_adapters, hipStream_t s);

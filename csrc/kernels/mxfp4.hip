@@ -21,27 +21,10 @@
 // Requires K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0), M <= 64, lda % 4 == 0, ldc % 4 == 0.
 #include "common.h"
 #include "launchers.h"
+#include "mxfp4_cvt.h"
 
 namespace lwc {
 namespace mxfp4 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-constexpr int KS = 8;  // waves per workgroup (split-K)
-
-// the e8m0 byte as the convert's f32 scale operand: 2^(s - 127) is the float with exponent field s
-LWC_DEVICE float e8m0(uint32_t s) { return __uint_as_float(s << 23); }
-
-// 8 codes (one dword: k ascending from the low nibble of byte 0) -> 8 bf16 in k order, times the block scale
-LWC_DEVICE uint4v cvt8(uint32_t q, float scale) {
-  uint4v r;
-  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 0));
-  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 1));
-  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 2));
-  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3));
-  return r;
-}
 
 // thread t: dword t of q (codes 8 t .. 8 t + 7 of the flat [N, K] weight), scale byte t / 4
 __global__ void __launch_bounds__(256) dequant_kernel(const uint32_t* __restrict__ q, const uint8_t* __restrict__ s,
@@ -49,11 +32,6 @@ __global__ void __launch_bounds__(256) dequant_kernel(const uint32_t* __restrict
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= n8) return;
   out[t] = cvt8(q[t], e8m0(s[t >> 2]));
-}
-
-LWC_DEVICE float4v mfma(const uint4v& a, const uint4v& b, const float4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                 0, 0);
 }
 
 struct Params {

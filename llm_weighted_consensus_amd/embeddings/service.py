@@ -92,7 +92,8 @@ def build_embedding_service(name: str, spec: dict, dev) -> "EmbeddingService":
     from ..models.config import DECODERS, check_variant, decoder_config, encoder_config
 
     check_variant(DECODERS.get(spec.get("arch")), mxfp4=bool(spec.get("mxfp4")), adapters=bool(spec.get("adapters")),
-                  embedder=True, who=f"embedding model {name}", mxfp4_act=spec.get("mxfp4_act"))
+                  embedder=True, who=f"embedding model {name}", mxfp4_act=spec.get("mxfp4_act"),
+                  expert_weights=spec.get("expert_weights"))
     w = spec.get("weights", "random:0")
     path, seed = (None, int(w.split(":", 1)[1])) if str(w).startswith("random:") else (w, 0)
     dev = torch.device(dev)

@@ -69,9 +69,14 @@ def check_decoder(cfg: DecoderConfig) -> None:
 MXFP4_ACTS = ("bf16", "e4m3")
 
 
+# formats of a MoE decoder's expert weights: "bf16" (or e4m3 with "fp8") or "mxfp4" (weight-only, ops.Mxfp4Experts)
+EXPERT_WEIGHTS = ("bf16", "mxfp4")
+
+
 def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool = False, mxfp4: bool = False,
                   adapters: bool = False, embedder: bool = False, device_type: Optional[str] = None,
-                  who: str = "", mxfp4_act: Optional[str] = None) -> None:
+                  who: str = "", mxfp4_act: Optional[str] = None, expert_weights: Optional[str] = None,
+                  ep: bool = False) -> None:
     """Refuse the decoder variants that do not combine (the model constructors, ``lora.check_model_spec`` and
     the embedding service all call this with the facts they know; ``cfg`` None: an arch not registered).
 
@@ -80,8 +85,36 @@ def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool =
     kernels only (``device_type``, where the caller has a device).  ``who`` prefixes the message.
 
     ``mxfp4_act`` (None: not given): the activation format of the MXFP4 projections, one of ``MXFP4_ACTS`` and only
-    together with mxfp4 weights; whatever mxfp4 weights refuse is refused first, in the same words."""
+    together with mxfp4 weights; whatever mxfp4 weights refuse is refused first, in the same words.
+
+    ``expert_weights`` (None: not given): the format of a MoE decoder's expert weights, one of ``EXPERT_WEIGHTS``.
+    "mxfp4" (ops.Mxfp4Experts, csrc/kernels/moe_mxfp4.hip) runs on one device (no ``tp``, no ``ep``: expert
+    parallelism), not with fp8 weights, adapters or as an embedder; the key is refused on a dense arch.  The dense
+    ``mxfp4`` flag stays refused on MoE decoders, in the words it always had."""
     moe = cfg is not None and bool(cfg.num_experts)
+    if expert_weights is not None:
+        # the experts' format (None: not given): "mxfp4" holds a MoE decoder's expert projections as MXFP4,
+        # weight-only, on one device and without fp8 weights or adapters; the key means nothing on a dense arch
+        why = None
+        if expert_weights not in EXPERT_WEIGHTS:
+            why = f"expert_weights {expert_weights!r}: must be one of {', '.join(repr(a) for a in EXPERT_WEIGHTS)}"
+        elif embedder and expert_weights == "mxfp4":
+            why = "mxfp4 expert weights are served on generation models only"
+        elif not moe:
+            why = ("expert_weights applies to MoE decoders only"
+                   + (f" ({cfg.name} is dense)" if cfg is not None else ""))
+        elif expert_weights == "mxfp4":
+            if fp8:
+                why = "mxfp4 expert weights do not combine with fp8 weights"
+            elif tp:
+                why = ("mxfp4 expert weights do not combine with "
+                       f"{'tp > 1' if who else 'tensor parallelism (tp > 1)'}")
+            elif ep:
+                why = "mxfp4 expert weights do not combine with expert parallelism (ep > 1)"
+            elif adapters:
+                why = "mxfp4 expert weights do not combine with LoRA adapters"
+        if why is not None:
+            raise ValueError(f"{who}: {why}" if who else why)
     if mxfp4_act is not None and not mxfp4:
         why = "\"mxfp4_act\" needs \"mxfp4\": true" if who else "mxfp4_act needs mxfp4=True"
         raise ValueError(f"{who}: {why}" if who else why)

@@ -13,6 +13,11 @@ changes.  Per layer, for the T tokens of a step:
 With ``fp8=True`` the expert weights are OCP e4m3 with per-output-channel scales (quantised at load)
 and activations are quantised per row on the fly (K11e), feeding the fp8 MFMA path of the grouped
 GEMM: half the weight bytes — what bounds a MoE decode step, which touches every expert's weights.
+With ``expert_weights="mxfp4"`` the expert gate|up and down stacks are held as MXFP4 (``ops.Mxfp4Experts``, 4.25
+bits per weight, quantised per expert at load) with bf16 activations; attention, router, embedding, norms and
+lm_head stay bf16.  Steps of up to ``ops.MOE_MXFP4_STREAM_AVG_ROWS`` rows per expert run the grouped weight stream
+of csrc/kernels/moe_mxfp4.hip, larger ones dequantise a stack into ``moe_scratch`` and run the bf16 grouped GEMM
+(``ops.moe_swiglu_mxfp4`` / ``ops.moe_linear_mxfp4``).  One device, no fp8, no adapters (``config.check_variant``).
 
 Tensor parallelism (``tp_group``): attention heads and every expert's FFN columns are split across
 the ranks (Megatron layout: q/k/v and gate|up column-parallel, o and down row-parallel); the two
@@ -52,11 +57,11 @@ class MoELayerWeights:
     wo: torch.Tensor
     mlp_norm: torch.Tensor
     router: torch.Tensor          # [E, d]
-    w13: torch.Tensor             # [E, 2F_local, d]  (bf16 or e4m3fn)
+    w13: torch.Tensor             # [E, 2F_local, d]  (bf16 or e4m3fn; ops.Mxfp4Experts with expert_weights="mxfp4")
     w2: torch.Tensor              # [E, d, F_local]
     s13: Optional[torch.Tensor]   # fp8 per-channel scales [E, 2F_local]
     s2: Optional[torch.Tensor]    # [E, d]
-    gu_block: int = 0             # >0: w13 rows interleave gate|up in blocks of this size (fp8 path)
+    gu_block: int = 0             # >0: w13 rows interleave gate|up in blocks of this size (fp8, mxfp4 experts)
     # the Qwen attention block's fields (LayerWeights): no MoE decoder has a q|k|v bias (the constructor refuses
     # the config); the per-head q / k norm weights [D] are set by models.qwen_moe.Qwen3MoeModel only
     bqkv: None = None
@@ -73,8 +78,11 @@ class MixtralModel(TensorParallel, LlamaModel):
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8: bool = False,
                  tp_rank: int = 0, tp_size: int = 1, tp_group=None, ep_rank: int = 0, ep_size: int = 1,
                  ep_group=None, ep_mode: str = "padded", ep_capacity: Optional[int] = None, tp_comm=None,
-                 ep_comm=None, mxfp4: bool = False):
-        check_variant(cfg, tp=tp_size > 1, fp8=fp8, mxfp4=mxfp4)
+                 ep_comm=None, mxfp4: bool = False, expert_weights: str = "bf16"):
+        # ("bf16", the default, is today's model and states nothing to check)
+        check_variant(cfg, tp=tp_size > 1, fp8=fp8, mxfp4=mxfp4, ep=ep_size > 1,
+                      expert_weights=None if expert_weights == "bf16" else expert_weights)
+        self.expert_weights = expert_weights
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
         if cfg.qkv_bias or (cfg.qk_norm and not self.qk_norm_attention):
@@ -106,6 +114,13 @@ class MixtralModel(TensorParallel, LlamaModel):
 
             self.cfg = replace(cfg, heads=cfg.heads // tp_size, kv_heads=cfg.kv_heads // tp_size)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        # MXFP4 experts: one dequantisation buffer of the larger stack's size (gate|up) for the steps past the
+        # weight stream's row limit, allocated here: never inside a capture
+        self.moe_scratch: Optional[torch.Tensor] = None
+        if self.expert_weights == "mxfp4" and self.on_gpu:
+            n = max(math.prod(w.shape) for L in self.layers for w in (L.w13, L.w2))
+            self.moe_scratch = torch.empty(n, dtype=torch.bfloat16, device=self.device)
+            torch.cuda.empty_cache()
 
     def tune_gemms(self, M: int, bucket: bool = False, lm_head: bool = True, only=None) -> None:
         """The bf16 vocabulary projection is the MoE decoder's one dense bf16 GEMM (attention projections and
@@ -142,8 +157,18 @@ class MixtralModel(TensorParallel, LlamaModel):
             w2_s, s2 = ops.quant_fp8_weight(w2_s)
             # the attention projections are fp8 too (config 5: fp8 MFMA throughout; router and lm_head bf16)
             wqkv, wo_s = ops.Fp8Weight(wqkv), ops.Fp8Weight(wo_s)
-        return MoELayerWeights(attn_norm, wqkv, wo_s, mlp_norm, router.contiguous(), w13, w2_s, s13, s2,
-                               32 if self.fp8 else 0)
+        gu_block = 32 if self.fp8 else 0
+        if self.expert_weights == "mxfp4":
+            # quantised expert by expert as each layer is built (the bf16 model is never resident); per row, so it
+            # commutes with the gate|up interleave.  A CPU device holds the dequantised bf16 stacks in the plain
+            # row order and runs the bf16 path
+            if self.on_gpu:
+                w13 = torch.stack([ops.swiglu_interleave(w13[e], 32) for e in range(w13.shape[0])])
+                gu_block = 32
+            w13, w2_s = ops.Mxfp4Experts(w13), ops.Mxfp4Experts(w2_s)
+            if not self.on_gpu:
+                w13, w2_s = w13.dequant(), w2_s.dequant()
+        return MoELayerWeights(attn_norm, wqkv, wo_s, mlp_norm, router.contiguous(), w13, w2_s, s13, s2, gu_block)
 
     def _random_init(self, seed: int) -> None:
         cfg, dev, dt = self.full_cfg, self.device, self.dtype
@@ -230,6 +255,9 @@ class MixtralModel(TensorParallel, LlamaModel):
                                    swiglu=True)
             aq, as_ = ops.quant_fp8_rows(act)
             return ops.grouped_gemm(aq, L.w2, row_off, a_scale=as_, w_scale=L.s2)
+        if isinstance(L.w13, ops.Mxfp4Experts):
+            act = ops.moe_swiglu_mxfp4(x, L.w13, row_off, a_rows, rows, self.moe_scratch)
+            return ops.moe_linear_mxfp4(act, L.w2, row_off, self.moe_scratch)
         gu = ops.grouped_gemm(x, L.w13, row_off, a_rows=a_rows, rows=rows)
         return ops.grouped_gemm(ops.silu_mul(gu), L.w2, row_off)
 

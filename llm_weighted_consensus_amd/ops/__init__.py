@@ -484,7 +484,7 @@ def skinny_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
 # MXFP4 weight-only projections (4-bit weights, bf16 activations): format and host quantiser in ops/mxfp4.py,
 # kernels in csrc/kernels/mxfp4.hip
 
-from .mxfp4 import Mxfp4Weight, check_mxfp4, dequant_mxfp4, quant_mxfp4_weight  # noqa: E402
+from .mxfp4 import Mxfp4Experts, Mxfp4Weight, check_mxfp4, dequant_mxfp4, quant_mxfp4_weight  # noqa: E402
 
 
 def mxfp4_dequant(w: Mxfp4Weight, out: torch.Tensor) -> torch.Tensor:
@@ -540,6 +540,91 @@ def swiglu_mxfp4(x: torch.Tensor, w: Mxfp4Weight, block: int, scratch: torch.Ten
     from . import gemm_plan
 
     return gemm_plan.swiglu(x, _mxfp4_scratch(w, scratch), block, ws=ws)
+
+
+# MoE experts in MXFP4 (csrc/kernels/moe_mxfp4.hip).  The expert FFN takes the grouped weight stream while the
+# (token, slot) rows per expert average at most this many, else it dequantises the stack and runs the bf16 grouped
+# GEMM: ``rows <= MOE_MXFP4_STREAM_AVG_ROWS * E``, from the rows of the step and the expert count alone.
+# Measured (profiles/moe_mxfp4.md, expert FFN of one layer, stream / dequantise time): at the qwen3-30b-a3b shapes
+# 0.39 / 0.42 / 0.47 / 0.61 at 4 / 8 / 16 / 32 rows per expert and 2.10 at 256; at the mixtral-8x7b shapes 0.23 /
+# 0.34 / 0.52 / 0.86 at 4 / 16 / 32 / 64 and 1.29 at 128.  32 is the largest average measured as a win at both; the
+# crossover lies between 64 and 128 (Mixtral) and between 32 and 256 (Qwen3-MoE, not measured in between).
+MOE_MXFP4_STREAM_AVG_ROWS = 32
+
+
+def moe_skinny_mxfp4_ok(a_nrows: int, lda: int, rows: int, w: Mxfp4Experts, swiglu: bool = False) -> bool:
+    """Whether :func:`moe_skinny_mxfp4` takes the shape: the kernel's divisibility rules, and everything its 32-bit
+    buffer offsets index (an expert's codes, the activation extent, ``a_rows``) below 2^31 bytes."""
+    E, N, K = w.shape
+    if K % 128 or N % (64 if swiglu else 16) or lda % 4 or lda < K or not 1 <= E <= 65535:
+        return False
+    return N * (K // 2) < (1 << 31) and a_nrows * lda * 2 < (1 << 31) and rows * 4 < (1 << 31)
+
+
+def moe_skinny_mxfp4(A: torch.Tensor, w: Mxfp4Experts, row_off: torch.Tensor, a_rows: Optional[torch.Tensor] = None,
+                     rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                     swiglu: bool = False) -> torch.Tensor:
+    """Grouped :func:`skinny_mxfp4` over an expert stack, one launch: rows ``[row_off[e], row_off[e + 1])`` of the
+    result are ``A[those rows] . W[e]^T`` (``swiglu``: over a 32-row gate/up interleaved W[e], output
+    ``[rows, N / 2]``), bit for bit what :func:`skinny_mxfp4` gives for any chunk of at most 64 of them.  ``a_rows``
+    ``[rows]`` int32 gathers A's row for each output row (the router's ``src_row``); without it A holds the
+    expert-major rows.  ``row_off`` ``[E + 1]`` int32 stays on the device: no host step, graph-capturable, correct for
+    any segment lengths (a long segment streams its weights once per 64 rows)."""
+    if rows is None:
+        rows = a_rows.numel() if a_rows is not None else A.shape[0]
+    if out is None:
+        out = torch.empty(rows, w.shape[1] // 2 if swiglu else w.shape[1], dtype=torch.bfloat16, device=A.device)
+    kernels().moe_skinny_mxfp4(A, w.q, w.s, out, row_off, a_rows, 2 if swiglu else 0)
+    return out
+
+
+def moe_dequant_mxfp4(w: Mxfp4Experts, scratch: torch.Tensor) -> torch.Tensor:
+    """The bf16 stack ``[E, N, K]`` of ``w`` at the front of ``scratch`` (caller-owned, contiguous bf16: safe inside
+    a captured graph), bitwise ``w.dequant()``."""
+    E, N, K = w.shape
+    if scratch.dtype != torch.bfloat16 or not scratch.is_contiguous() or scratch.numel() < E * N * K:
+        raise ValueError(f"MXFP4 expert scratch: a contiguous bf16 buffer of at least {E * N * K} elements, got "
+                         f"{scratch.dtype} x {scratch.numel()}")
+    out = scratch.view(-1)[:E * N * K].view(E * N, K)
+    kernels().mxfp4_dequant(w.q.view(E * N, K // 2), w.s.view(E * N, K // 32), out)
+    return out.view(E, N, K)
+
+
+def _moe_mxfp4_stream(path: Optional[str], rows: int, ok: bool, E: int) -> bool:
+    if path not in (None, "stream", "dequant"):
+        raise ValueError(f"MXFP4 experts: path {path!r} must be 'stream', 'dequant' or None")
+    if path == "stream" and not ok:
+        raise ValueError("MXFP4 experts: the grouped weight-stream kernel does not take this shape")
+    return ok and (path == "stream" or (path is None and rows <= MOE_MXFP4_STREAM_AVG_ROWS * E))
+
+
+def moe_swiglu_mxfp4(x: torch.Tensor, w13: Mxfp4Experts, row_off: torch.Tensor, a_rows: Optional[torch.Tensor],
+                     rows: Optional[int], scratch: torch.Tensor, path: Optional[str] = None) -> torch.Tensor:
+    """The experts' gate|up projection with its SwiGLU over an MXFP4 stack whose rows interleave gate / up in blocks
+    of 32 per expert -> ``[rows, F]`` bf16, expert-major.  Up to ``MOE_MXFP4_STREAM_AVG_ROWS`` rows per expert on
+    average (``rows`` and E alone decide, never a timing) the grouped weight stream :func:`moe_skinny_mxfp4`; past
+    that, or for a shape the stream kernel does not index, the stack is dequantised into ``scratch`` (one bf16
+    buffer of the larger stack's size, owned by the model, never allocated inside a capture) and the bf16
+    :func:`grouped_gemm` + :func:`silu_mul` run on it.  ``path``: "stream" / "dequant" forces one (tests, benches)."""
+    if rows is None:
+        rows = a_rows.numel() if a_rows is not None else x.shape[0]
+    ok = (x.dim() == 2 and x.stride(1) == 1
+          and moe_skinny_mxfp4_ok(x.shape[0], x.stride(0), rows, w13, swiglu=True))
+    if _moe_mxfp4_stream(path, rows, ok, w13.shape[0]):
+        return moe_skinny_mxfp4(x, w13, row_off, a_rows=a_rows, rows=rows, swiglu=True)
+    gu = grouped_gemm(x, moe_dequant_mxfp4(w13, scratch), row_off, a_rows=a_rows, rows=rows)
+    return silu_mul(gu, block=32)
+
+
+def moe_linear_mxfp4(act: torch.Tensor, w2: Mxfp4Experts, row_off: torch.Tensor, scratch: torch.Tensor,
+                     path: Optional[str] = None) -> torch.Tensor:
+    """The experts' down projection of expert-major rows over an MXFP4 stack -> ``[rows, d]`` bf16; routed as
+    :func:`moe_swiglu_mxfp4`."""
+    rows = act.shape[0]
+    ok = act.dim() == 2 and act.stride(1) == 1 and moe_skinny_mxfp4_ok(rows, act.stride(0), rows, w2)
+    if _moe_mxfp4_stream(path, rows, ok, w2.shape[0]):
+        return moe_skinny_mxfp4(act, w2, row_off)
+    return grouped_gemm(act, moe_dequant_mxfp4(w2, scratch), row_off)
 
 
 # W4A8: e4m3 activations x the packed MXFP4 weight on the block-scaled MFMA (csrc/kernels/mxfp4_a8.hip).  A model

@@ -115,3 +115,36 @@ class Mxfp4Weight:
 
     def dequant(self) -> torch.Tensor:
         return dequant_mxfp4(self.q, self.s)
+
+
+class Mxfp4Experts:
+    """A stack of E expert projection weights in MXFP4 (``shape`` = (E, N, K)): ``q`` uint8 ``[E, N, K / 2]`` and
+    ``s`` uint8 ``[E, N, K / 32]``, each expert in the format above, contiguous.  Built from the bf16 stack one
+    expert at a time; the grouped kernel (``csrc/kernels/moe_mxfp4.hip``) reads it as stored: nothing is
+    repacked."""
+
+    __slots__ = ("q", "s", "shape")
+
+    def __init__(self, w: torch.Tensor):
+        if w.dim() != 3 or w.shape[2] % BLOCK:
+            raise ValueError(f"Mxfp4Experts: W {tuple(w.shape)} must be [E, N, K] with K % {BLOCK} == 0")
+        E, N, K = w.shape
+        self.q = torch.empty(E, N, K // 2, dtype=torch.uint8, device=w.device)
+        self.s = torch.empty(E, N, K // BLOCK, dtype=torch.uint8, device=w.device)
+        for e in range(E):
+            self.q[e], self.s[e] = quant_mxfp4_weight(w[e])
+        self.shape = (E, N, K)
+
+    @property
+    def nbytes(self) -> int:
+        return self.q.numel() + self.s.numel()
+
+    def expert(self, e: int) -> Mxfp4Weight:
+        """Expert ``e`` as a dense weight: a view, no copy."""
+        w = Mxfp4Weight.__new__(Mxfp4Weight)
+        w.q, w.s, w.shape = self.q[e], self.s[e], self.shape[1:]
+        return w
+
+    def dequant(self) -> torch.Tensor:
+        """The bf16 stack ``[E, N, K]``, exact."""
+        return torch.stack([dequant_mxfp4(self.q[e], self.s[e]) for e in range(self.shape[0])])

@@ -26,6 +26,13 @@ variables configure the local engine:
                     activations on the block-scaled MFMA, reading the packed weight directly (no
                     dequantisation pass, no scratch buffer; csrc/kernels/mxfp4_a8.hip); smaller calls stay
                     the bf16-activation weight stream.  Refused without "mxfp4": true and for any other value
+                    "expert_weights": "mxfp4" (MoE archs; default "bf16") holds every expert's gate|up and down
+                    projection as MXFP4 (ops.Mxfp4Experts, 4.25 bits per weight) with bf16 activations;
+                    attention, router, embedding, norms and lm_head stay bf16, and the memory saved becomes KV
+                    blocks.  Quantised at load, per expert; small steps run the grouped weight stream of
+                    csrc/kernels/moe_mxfp4.hip, large ones dequantise into a scratch and run the bf16 grouped
+                    GEMM.  Refused for any other value, on dense archs, with "fp8", "tp" > 1, "adapters" and
+                    in LWC_EMBED_MODELS; "mxfp4": true stays refused on MoE archs
   LWC_EMBED_MODELS  JSON {name: {"arch": "bge-large-en-v1.5", "weights": "random:<seed>" | <path>}}
   LWC_GPU           device index for this process's engine (one process per GPU)
   LWC_GPUS          comma list of devices: serve each model through an EngineGroup (one worker process

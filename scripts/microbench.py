@@ -1325,6 +1325,119 @@ def qwen_moe(dev):
     print("wrote", out)
 
 
+def moe_mxfp4_ab(dev):
+    """MoE experts in MXFP4 (profiles/moe_mxfp4.md).  (a) the expert FFN of one layer (gate|up + SwiGLU + down, rows
+    routed by ``ops.route`` on N(0, 1) tokens) at the qwen3-30b-a3b and mixtral-8x7b expert shapes: bf16 experts,
+    fp8 experts, the MXFP4 grouped weight stream and the MXFP4 dequantise path; (b) one qwen3-30b-a3b decode step at
+    4 layers, bf16 vs ``expert_weights="mxfp4"``; (c) GiB allocated after the load.  Arms interleaved in one
+    process, medians of 7 rounds of captured graphs; the MXFP4 stacks rotate over 3 copies where one would fit the
+    last-level cache."""
+    from pathlib import Path
+    from types import SimpleNamespace
+
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.mixtral import MixtralModel, MoELayerWeights
+    from llm_weighted_consensus_amd.models.qwen_moe import Qwen3MoeModel
+
+    out = Path(os.environ.get("MOEMXFP4_OUT", Path(__file__).resolve().parent.parent / "profiles" / "moe_mxfp4.md"))
+    Ts = [int(t) for t in os.environ.get("MOEMXFP4_T", "1,16,64,128,256,512,4096").split(",")]
+    lines = ["# MoE experts in MXFP4: the grouped weight stream (`python scripts/microbench.py moemxfp4`)", "",
+             f"MI355X, torch {torch.__version__}.  Arms interleaved in one process, median of 7 rounds; every arm is a "
+             "captured graph of several calls.", "",
+             "## (a) Expert FFN of one layer: gate|up + SwiGLU + down", "",
+             "Rows are the (token, slot) pairs `ops.route` makes of T N(0, 1) tokens and a random router.  bf16: "
+             "`grouped_gemm`, `silu_mul`, `grouped_gemm`; fp8: the model's fp8 branch on rows quantised outside the "
+             "timing; stream: `moe_skinny_mxfp4` twice; dequant: `mxfp4_dequant` of each stack into the scratch, then "
+             "the bf16 arm.  GB/s: the bytes of the active experts' weights in the arm's format over the time.", "",
+             "| shapes | T | rows / expert | active | bf16 us (GB/s) | fp8 us (GB/s) | stream us (GB/s) | dequant us (GB/s) "
+             "| stream / dequant | stream / bf16 |", "|---|---|---|---|---|---|---|---|---|---|"]
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*shape, std=0.02):
+        return (torch.randn(*shape, device=dev, generator=g) * std).to(torch.bfloat16)
+
+    def rand_stack(E, N, K):  # timing only: any codes, scales near 2^-6
+        st = ops.Mxfp4Experts.__new__(ops.Mxfp4Experts)
+        st.q = torch.randint(0, 256, (E, N, K // 2), device=dev, dtype=torch.uint8)
+        st.s = torch.randint(117, 125, (E, N, K // 32), device=dev, dtype=torch.uint8)
+        st.shape = (E, N, K)
+        return st
+
+    crossover = {}
+    for arch in ("qwen3-30b-a3b", "mixtral-8x7b"):
+        cfg = decoder_config(arch)
+        d, F_, E, k = cfg.hidden, cfg.ffn, cfg.num_experts, cfg.experts_per_token
+        w13 = torch.stack([ops.swiglu_interleave(rnd(2 * F_, d)) for _ in range(E)])
+        w2 = rnd(E, d, F_)
+        q13, s13 = ops.quant_fp8_weight(w13)
+        q2, s2 = ops.quant_fp8_weight(w2)
+        copies = 3 if E * 3 * F_ * d * 17 // 32 < (512 << 20) else 1
+        mx = _rotating([(rand_stack(E, 2 * F_, d), rand_stack(E, d, F_)) for _ in range(copies)])
+        scratch = torch.empty(E * 2 * F_ * d, dtype=torch.bfloat16, device=dev)
+        router = rnd(E, d, std=0.1)
+        me = SimpleNamespace(fp8=True, moe_scratch=scratch)
+        L8 = MoELayerWeights(None, None, None, None, router, q13, q2, s13, s2, 32)
+        per_expert = 3 * F_ * d
+        for T in Ts:
+            h = torch.randn(T, d, device=dev, generator=g).to(torch.bfloat16)
+            _, _, row_off, src, _ = ops.route(h, router, k)
+            rows = T * k
+            active = int((row_off.diff() > 0).sum())
+            hq, hs = ops.quant_fp8_rows(h)
+
+            def bf16():
+                gu = ops.grouped_gemm(h, w13, row_off, a_rows=src, rows=rows)
+                return ops.grouped_gemm(ops.silu_mul(gu, block=32), w2, row_off)
+
+            def mxfp4(path):
+                a, b = mx()
+                act = ops.moe_swiglu_mxfp4(h, a, row_off, src, rows, scratch, path=path)
+                return ops.moe_linear_mxfp4(act, b, row_off, scratch, path=path)
+
+            t = _graph_medians({"bf16": bf16,
+                                "fp8": lambda: MixtralModel._experts(me, hq, row_off, L8, hs, a_rows=src, rows=rows),
+                                "stream": lambda: mxfp4("stream"), "dequant": lambda: mxfp4("dequant")},
+                               10 if rows <= 1024 else 3)
+            gbs = {a: active * per_expert * b / t[a] / 1e3 for a, b in
+                   (("bf16", 2), ("fp8", 1), ("stream", 17 / 32), ("dequant", 17 / 32))}
+            r1, r2 = t["stream"] / t["dequant"], t["stream"] / t["bf16"]
+            cells = [f"**{r:.2f} (slower)**" if r > 1 else f"{r:.2f}" for r in (r1, r2)]
+            lines.append(f"| {arch} | {T} | {rows / E:.2f} | {active} / {E} | "
+                         + " | ".join(f"{t[a]:.1f} ({gbs[a]:.0f})" for a in ("bf16", "fp8", "stream", "dequant"))
+                         + f" | {cells[0]} | {cells[1]} |")
+            print(lines[-1], flush=True)
+            crossover.setdefault(arch, []).append((rows / E, r1))
+        del w13, w2, q13, q2, s13, s2, mx, scratch, L8, me
+        torch.cuda.empty_cache()
+    lines += ["", "Crossover (largest measured rows / expert at which the stream path is still no slower than the "
+              "dequantise path): " + "; ".join(
+                  f"{a}: {max([r for r, x in v if x <= 1] or [0]):.2f}" for a, v in crossover.items()) + "."]
+
+    lines += ["", "## (b) One decode step, qwen3-30b-a3b shapes at 4 layers (context 32, captured graph)", "",
+              "| experts | B | step ms | vs bf16 |", "|---|---|---|---|"]
+    cfg = decoder_config("qwen3-30b-a3b", layers=4)
+    gib, base = {}, {}
+    for fmt in ("bf16", "mxfp4"):
+        torch.cuda.empty_cache()
+        before = torch.cuda.memory_allocated(dev)
+        model = Qwen3MoeModel(cfg, device=dev, seed=0, max_position=128, expert_weights=fmt)
+        torch.cuda.synchronize()
+        gib[fmt] = (torch.cuda.memory_allocated(dev) - before) / 2 ** 30
+        for B in (64, 512, 4096):
+            step = _decode_step_ms(model, cfg, dev, B)[0]
+            base.setdefault(B, step)
+            r = step / base[B]
+            lines.append(f"| {fmt} | {B} | {step:.3f} | " + (f"**{r:.2f} (slower)**" if r > 1 else f"{r:.2f}") + " |")
+            print(lines[-1], flush=True)
+        del model
+    lines += ["", "## (c) GiB allocated after the load (qwen3-30b-a3b shapes at 4 layers, scratch included)", "",
+              "| experts | GiB |", "|---|---|"] + [f"| {f} | {v:.2f} |" for f, v in gib.items()]
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["gemm", "attn", "sample", "small"])
@@ -1360,6 +1473,8 @@ def main():
         qknorm(dev)
     if "qwenmoe" in a.what:
         qwen_moe(dev)
+    if "moemxfp4" in a.what:
+        moe_mxfp4_ab(dev)
     if "g48" in a.what:
         g48_ab(dev)
     if "g8ab" in a.what:
