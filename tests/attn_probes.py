@@ -289,13 +289,14 @@ def softmax_out(s: torch.Tensor, v: torch.Tensor, drop: Optional[int] = None, do
 
 
 def emulate(s: torch.Tensor, v: torch.Tensor, tiles: Optional[Sequence[Tuple[int, int]]] = None, *,
-            skip_o_rescale: bool = False, alpha_shift: int = 0) -> torch.Tensor:
+            skip_o_rescale: bool = False, alpha_shift: int = 0, state: bool = False) -> torch.Tensor:
     """The kernels' recurrence for the rows of one wave: s [R, L] scores (nats, -inf = masked), v [L, D] bf16
     values, ``tiles`` = key ranges in processing order (default: 32-key tiles from 0).  fp32 state in the log2
     domain; the running max m moves, and O and l are rescaled, only when some row's tile max exceeds its m by
     more than LAZY_LOG2 (one decision for the whole wave); P is rounded to bf16 for P V but summed unrounded
     into l; the output is rounded to bf16.  ``skip_o_rescale`` leaves O unscaled in that branch;
-    ``alpha_shift`` = n scales row r of O by the alpha of row r - n."""
+    ``alpha_shift`` = n scales row r of O by the alpha of row r - n.  ``state``: return the fp32 (o / l, l) before
+    the bf16 store (what the cascade kernel's MX epilogue quantises)."""
     R, L = s.shape
     s2 = (s.double() * LOG2E).float()
     vf = v.float()
@@ -316,4 +317,6 @@ def emulate(s: torch.Tensor, v: torch.Tensor, tiles: Optional[Sequence[Tuple[int
         l = l + p.sum(1)
         o = o + p.to(torch.bfloat16).float() @ vf[a:b]
     inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
+    if state:
+        return o * inv[:, None], l
     return (o * inv[:, None]).to(torch.bfloat16).float()
