@@ -12,7 +12,10 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KS = 8;  // waves per workgroup (split-K)
 
-// the e8m0 byte as the convert's f32 scale operand: 2^(s - 127) is the float with exponent field s
+// the e8m0 byte as the convert's f32 scale operand: 2^(s - 127) is the float with exponent field s.  Byte 0 makes
+// this the float 0.0, and the convert still scales by 2^-127 (it takes the operand's exponent field as the e8m0
+// byte), keeps bf16 subnormal results and gives inf where byte 253 / 254 overflow: the host function on all
+// 16 x 255 pairs, pinned on an MI355X by tests/test_mxw_probes_gpu.py
 LWC_DEVICE float e8m0(uint32_t s) { return __uint_as_float(s << 23); }
 
 // 8 codes (one dword: k ascending from the low nibble of byte 0) -> 8 bf16 in k order, times the block scale

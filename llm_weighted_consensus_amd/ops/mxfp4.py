@@ -7,6 +7,10 @@ A block is 32 consecutive k of one output row of ``W [N, K]`` (``K % 32 == 0``).
 
 Every e2m1 x 2^e value is a bf16, so the dequantised weight is a bf16 tensor and every bf16 kernel and fp32
 oracle of the project applies to it unchanged.  The device kernels are in ``csrc/kernels/mxfp4.hip``.
+
+Every byte from 0 to 254 is in: ``dequant_mxfp4`` is the law, and the device readers follow it on all 16 x 255
+(code, byte) pairs, byte 0 (2^-127, bf16-subnormal values) and the ``inf`` of bytes 253 and 254 included
+(``tests/test_mxw_probes_gpu.py``, measured on an MI355X).
 """
 from __future__ import annotations
 
