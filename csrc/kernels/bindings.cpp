@@ -576,6 +576,49 @@ void moe_skinny_mxfp4(const at::Tensor& A, const at::Tensor& q, const at::Tensor
            who);
 }
 
+// grouped W4A8 GEMM over a stack of MXFP4 expert weights (moe_mxfp4_a8.hip): rows [row_off[e], row_off[e + 1]) of C
+// are expert e's, computed from the e4m3 row A[a_rows[row]] and its scale a_scale[a_rows[row]] (a_rows given) or
+// A[row], a_scale[row]; any segment lengths
+void moe_gemm_mxfp4_a8(const at::Tensor& A, const at::Tensor& a_scale, const at::Tensor& q, const at::Tensor& s,
+                       at::Tensor& C, const at::Tensor& row_off, const OptTensor& a_rows, int64_t epi) {
+  const char* who = "moe_gemm_mxfp4_a8";
+  TORCH_CHECK(epi == 0 || epi == 2, who, ": epi 0 (plain) or 2 (SwiGLU)");
+  const void *qp = flat(q, U8, who, "q"), *sp = flat(s, U8, who, "s");
+  TORCH_CHECK(q.dim() == 3 && s.dim() == 3 && s.size(0) == q.size(0) && s.size(1) == q.size(1) &&
+                  q.size(2) == 16 * s.size(2),
+              who, ": q must be [E, N, K / 2] and s [E, N, K / 32] with K % 32 == 0");
+  TORCH_CHECK(A.scalar_type() == FP8, who, ": A must be float8_e4m3fn, got ", A.scalar_type());
+  const Strided a = strided(A, FP8, who, "A"), c = strided(C, BF16, who, "C");
+  const int64_t E = q.size(0), N = q.size(1), K = A.size(1), rows = C.size(0), a_nrows = A.size(0);
+  const int64_t NC = epi == 2 ? N / 2 : N;
+  TORCH_CHECK(2 * q.size(2) == K && C.size(1) == NC, who, ": shape mismatch (A [", a_nrows, ", ", K, "], W [", E, ", ",
+              N, ", ", 2 * q.size(2), "], C [", rows, ", ", C.size(1), "])");
+  TORCH_CHECK(a_scale.numel() == a_nrows, who, ": a_scale must hold one scale per row of A (", a_nrows, "), got ",
+              a_scale.numel());
+  const float* as = flat<float>(a_scale, F32, who, "a_scale");
+  TORCH_CHECK(K > 0 && K % 128 == 0 && N % (epi == 2 ? 64 : 16) == 0, who,
+              ": needs K % 128 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0); got K = ", K, ", N = ", N);
+  TORCH_CHECK(E >= 1 && E <= INT_MAX && rows <= INT_MAX && N <= INT_MAX && K <= INT_MAX, who,
+              ": E must be at least 1; E, rows, N and K below 2^31");
+  TORCH_CHECK(row_off.dim() == 1, who, ": row_off must be 1-D [E + 1]");
+  const int* ro = flat<int>(row_off, I32, who, "row_off", exactly(E + 1));
+  const int* ar = opt_flat<int>(a_rows, I32, who, "a_rows", exactly(rows));
+  TORCH_CHECK(present(a_rows) || a_nrows >= rows, who, ": without a_rows A must hold C's ", rows, " rows, has ",
+              a_nrows);
+  TORCH_CHECK((a_nrows <= 1 || (a.ld % 16 == 0 && a.ld >= K)) && (rows <= 1 || c.ld >= NC), who,
+              ": rows of A must be 16-byte aligned, rows of A / C must not overlap");
+  TORCH_CHECK((uintptr_t)a.p % 16 == 0 && (uintptr_t)qp % 16 == 0 && (uintptr_t)sp % 4 == 0, who,
+              ": A and the weights' codes must be 16-byte aligned, their scales 4-byte aligned");
+  const long long slots = (rows + 127) / 128 + E, n8 = ((N + 127) / 128 + 7) / 8;
+  TORCH_CHECK(slots * n8 * 8 < (1LL << 31), who, ": the grid of ", slots, " m-tile slots x ", n8 * 8,
+              " n-tiles is past 2^31 - 1 workgroups");
+  // (a single row's stride is arbitrary in torch: hand the kernel one that passes its own checks)
+  const int64_t lda = a_nrows <= 1 ? K : a.ld, ldc = rows <= 1 ? NC : c.ld;
+  CHECK_RC(lwc_moe_gemm_mxfp4_a8(a.p, as, qp, sp, c.p, ro, ar, (int)E, (int)rows, (long long)a_nrows, (int)N, (int)K,
+                                 (int)lda, (int)ldc, (int)epi, cur_stream()),
+           who);
+}
+
 // batched LoRA (lora.hip): T[m] = X[m] . A[ids[m]]^T, then Y[m] += T[m] . B[ids[m]]^T; ids outside
 // [0, n_adapters) (-1) mean no adapter: the row of T is not written, the row of Y not touched
 const int* lora_check_ids(const at::Tensor& ids, int64_t M, const char* who) {
@@ -1072,6 +1115,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_mxfp4", &skinny_mxfp4);
   m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8);
   m.def("moe_skinny_mxfp4", &moe_skinny_mxfp4);
+  m.def("moe_gemm_mxfp4_a8", &moe_gemm_mxfp4_a8);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand_add", &lora_expand_add);
   m.def("rms_rowsumsq", &rms_rowsumsq);

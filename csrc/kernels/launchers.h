@@ -87,6 +87,10 @@ int lwc_gemm_mxfp4_a8(const void* A, const float* a_scale, const void* Q, const 
 int lwc_moe_skinny_mxfp4(const void* A, const void* Q, const void* S, void* C, const int* row_off, const int* a_rows,
                          int E, long long rows, long long a_nrows, int N, int K, int lda, int ldc, int epi,
                          hipStream_t s);
+// ---- moe_mxfp4_a8.hip: the same stack; A e4m3 [a_nrows, lda], a_scale [a_nrows] (both read through a_rows)
+int lwc_moe_gemm_mxfp4_a8(const void* A, const float* a_scale, const void* Q, const void* S, void* C,
+                          const int* row_off, const int* a_rows, int E, int rows, long long a_nrows, int N, int K,
+                          int lda, int ldc, int epi, hipStream_t s);
 
 // ---- lora.hip: A [n_adapters, R, K], B [n_adapters, N, R], ids [M]
 int lwc_lora_shrink(const void* X, const void* A, const int* ids, void* T, int M, int K, int R, int ldx,

@@ -93,7 +93,7 @@ def build_embedding_service(name: str, spec: dict, dev) -> "EmbeddingService":
 
     check_variant(DECODERS.get(spec.get("arch")), mxfp4=bool(spec.get("mxfp4")), adapters=bool(spec.get("adapters")),
                   embedder=True, who=f"embedding model {name}", mxfp4_act=spec.get("mxfp4_act"),
-                  expert_weights=spec.get("expert_weights"))
+                  expert_weights=spec.get("expert_weights"), expert_act=spec.get("expert_act"))
     w = spec.get("weights", "random:0")
     path, seed = (None, int(w.split(":", 1)[1])) if str(w).startswith("random:") else (w, 0)
     dev = torch.device(dev)

@@ -726,6 +726,7 @@ def build_engine(spec: dict, wid: int):
     ({"arch", "weights": "random:<seed>" | path, "max_model_len", "max_batch", "kv_fraction", "fp8",
     "mxfp4": MXFP4 weight-only projections (ops/mxfp4.py), "mxfp4_act": "bf16" | "e4m3" their activation format,
     "expert_weights": "bf16" | "mxfp4" a MoE decoder's expert stacks (ops.Mxfp4Experts: weight-only, one device),
+    "expert_act": "bf16" | "e4m3" the activation format of MXFP4 experts past the weight stream's row limit,
     "prefix_caching", "chunked_prefill", "constrained_logprobs", "tokenizer": path to a tokenizer.json,
     "adapters": {name: adapter spec} — LoRA adapters served as "<model>:<name>", models/lora.py}); MoE archs get
     the Mixtral model, those with ``qk_norm`` the Qwen3-MoE one."""
@@ -761,7 +762,7 @@ def build_engine(spec: dict, wid: int):
         moe_cls = Qwen3MoeModel if cfg.qk_norm else MixtralModel  # (tp > 1 was refused above for Qwen3-MoE)
         model = moe_cls(cfg, device=dev, seed=seed, weights_path=path, max_position=mlen + 64,
                         fp8=bool(spec.get("fp8", False)), expert_weights=spec.get("expert_weights") or "bf16",
-                        **tp_kw)
+                        expert_act=spec.get("expert_act") or "bf16", **tp_kw)
         if tp > 1:
             num_blocks = _tp_num_blocks(model, dev, kv_fraction)
     elif tp > 1:

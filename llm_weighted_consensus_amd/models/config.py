@@ -73,10 +73,15 @@ MXFP4_ACTS = ("bf16", "e4m3")
 EXPERT_WEIGHTS = ("bf16", "mxfp4")
 
 
+# activation formats of MXFP4 experts: "bf16" (weight-only) or "e4m3" (W4A8 past the weight stream's row limit,
+# ops.moe_gemm_mxfp4_a8)
+EXPERT_ACTS = ("bf16", "e4m3")
+
+
 def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool = False, mxfp4: bool = False,
                   adapters: bool = False, embedder: bool = False, device_type: Optional[str] = None,
                   who: str = "", mxfp4_act: Optional[str] = None, expert_weights: Optional[str] = None,
-                  ep: bool = False) -> None:
+                  ep: bool = False, expert_act: Optional[str] = None) -> None:
     """Refuse the decoder variants that do not combine (the model constructors, ``lora.check_model_spec`` and
     the embedding service all call this with the facts they know; ``cfg`` None: an arch not registered).
 
@@ -90,7 +95,11 @@ def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool =
     ``expert_weights`` (None: not given): the format of a MoE decoder's expert weights, one of ``EXPERT_WEIGHTS``.
     "mxfp4" (ops.Mxfp4Experts, csrc/kernels/moe_mxfp4.hip) runs on one device (no ``tp``, no ``ep``: expert
     parallelism), not with fp8 weights, adapters or as an embedder; the key is refused on a dense arch.  The dense
-    ``mxfp4`` flag stays refused on MoE decoders, in the words it always had."""
+    ``mxfp4`` flag stays refused on MoE decoders, in the words it always had.
+
+    ``expert_act`` (None: not given): the activation format of MXFP4 experts, one of ``EXPERT_ACTS`` and only
+    together with ``expert_weights`` "mxfp4"; whatever ``expert_weights`` refuses is refused first, in the same
+    words."""
     moe = cfg is not None and bool(cfg.num_experts)
     if expert_weights is not None:
         # the experts' format (None: not given): "mxfp4" holds a MoE decoder's expert projections as MXFP4,
@@ -113,6 +122,15 @@ def check_variant(cfg: Optional[DecoderConfig], *, tp: bool = False, fp8: bool =
                 why = "mxfp4 expert weights do not combine with expert parallelism (ep > 1)"
             elif adapters:
                 why = "mxfp4 expert weights do not combine with LoRA adapters"
+        if why is not None:
+            raise ValueError(f"{who}: {why}" if who else why)
+    if expert_act is not None:
+        why = None
+        if expert_weights != "mxfp4":
+            why = ("\"expert_act\" needs \"expert_weights\": \"mxfp4\"" if who
+                   else "expert_act needs expert_weights=\"mxfp4\"")
+        elif expert_act not in EXPERT_ACTS:
+            why = f"expert_act {expert_act!r}: must be one of {', '.join(repr(a) for a in EXPERT_ACTS)}"
         if why is not None:
             raise ValueError(f"{who}: {why}" if who else why)
     if mxfp4_act is not None and not mxfp4:

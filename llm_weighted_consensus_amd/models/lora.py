@@ -137,7 +137,7 @@ def load_adapter(name: str, spec: dict, cfg: DecoderConfig) -> Adapter:
 
 def check_model_spec(name: str, spec: dict, embedder: bool = False) -> Tuple[str, ...]:
     """The adapter names of a server model spec, refusing the combinations adapters do not run in (tensor
-    parallelism, MoE decoders, fp8 weights, embedding models), what "mxfp4" / "mxfp4_act" / "expert_weights" do not
+    parallelism, MoE decoders, fp8 weights, embedding models), what "mxfp4" / "mxfp4_act" / "expert_weights" / "expert_act" do not
     run in (``config.check_variant``) and malformed adapter entries: raised when the server is configured, before
     any weight is loaded."""
     from .config import DECODERS, check_variant
@@ -145,7 +145,7 @@ def check_model_spec(name: str, spec: dict, embedder: bool = False) -> Tuple[str
     ads = spec.get("adapters")
     check_variant(DECODERS.get(spec.get("arch")), tp=int(spec.get("tp", 1) or 1) > 1, fp8=bool(spec.get("fp8")),
                   mxfp4=bool(spec.get("mxfp4")), adapters=bool(ads), embedder=embedder, mxfp4_act=spec.get("mxfp4_act"),
-                  expert_weights=spec.get("expert_weights"),
+                  expert_weights=spec.get("expert_weights"), expert_act=spec.get("expert_act"),
                   who=f"embedding model {name}" if embedder else f"model {name}")
     if not ads:
         return ()

@@ -18,6 +18,11 @@ bits per weight, quantised per expert at load) with bf16 activations; attention,
 lm_head stay bf16.  Steps of up to ``ops.MOE_MXFP4_STREAM_AVG_ROWS`` rows per expert run the grouped weight stream
 of csrc/kernels/moe_mxfp4.hip, larger ones dequantise a stack into ``moe_scratch`` and run the bf16 grouped GEMM
 (``ops.moe_swiglu_mxfp4`` / ``ops.moe_linear_mxfp4``).  One device, no fp8, no adapters (``config.check_variant``).
+With ``expert_act="e4m3"`` on top, the steps past that row limit quantise the token rows and the SwiGLU output per
+row to e4m3 and multiply them with the packed stacks on the block-scaled MFMA (csrc/kernels/moe_mxfp4_a8.hip,
+``ops.moe_swiglu_mxfp4_a8`` / ``ops.moe_linear_mxfp4_a8``): nothing is dequantised, and ``moe_scratch`` is not
+allocated where the kernel takes every layer's stacks.  The route is ``ops.moe_mxfp4_a8_route``: the step's routed
+rows and the expert count alone.  The weight stream keeps its bf16 activations.
 
 Tensor parallelism (``tp_group``): attention heads and every expert's FFN columns are split across
 the ranks (Megatron layout: q/k/v and gate|up column-parallel, o and down row-parallel); the two
@@ -78,11 +83,13 @@ class MixtralModel(TensorParallel, LlamaModel):
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8: bool = False,
                  tp_rank: int = 0, tp_size: int = 1, tp_group=None, ep_rank: int = 0, ep_size: int = 1,
                  ep_group=None, ep_mode: str = "padded", ep_capacity: Optional[int] = None, tp_comm=None,
-                 ep_comm=None, mxfp4: bool = False, expert_weights: str = "bf16"):
+                 ep_comm=None, mxfp4: bool = False, expert_weights: str = "bf16", expert_act: str = "bf16"):
         # ("bf16", the default, is today's model and states nothing to check)
         check_variant(cfg, tp=tp_size > 1, fp8=fp8, mxfp4=mxfp4, ep=ep_size > 1,
-                      expert_weights=None if expert_weights == "bf16" else expert_weights)
+                      expert_weights=None if expert_weights == "bf16" else expert_weights,
+                      expert_act=None if expert_act == "bf16" else expert_act)
         self.expert_weights = expert_weights
+        self.expert_act = expert_act
         if not cfg.num_experts:
             raise ValueError(f"{cfg.name} is dense; use LlamaModel")
         if cfg.qkv_bias or (cfg.qk_norm and not self.qk_norm_attention):
@@ -115,12 +122,22 @@ class MixtralModel(TensorParallel, LlamaModel):
             self.cfg = replace(cfg, heads=cfg.heads // tp_size, kv_heads=cfg.kv_heads // tp_size)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
         # MXFP4 experts: one dequantisation buffer of the larger stack's size (gate|up) for the steps past the
-        # weight stream's row limit, allocated here: never inside a capture
+        # weight stream's row limit, allocated here: never inside a capture.  With e4m3 activations those steps
+        # read the packed stacks, and the buffer exists only for a stack neither kernel takes at every row count
         self.moe_scratch: Optional[torch.Tensor] = None
-        if self.expert_weights == "mxfp4" and self.on_gpu:
+        if self.expert_weights == "mxfp4" and self.on_gpu and not (
+                self.expert_act == "e4m3" and all(self._a8_stacks_ok(L) for L in self.layers)):
             n = max(math.prod(w.shape) for L in self.layers for w in (L.w13, L.w2))
             self.moe_scratch = torch.empty(n, dtype=torch.bfloat16, device=self.device)
             torch.cuda.empty_cache()
+
+    @staticmethod
+    def _a8_stacks_ok(L) -> bool:
+        """Whether a layer's expert FFN never needs the dequantised stack: the W4A8 kernel takes both stacks at
+        any row count (the activations it is given are contiguous e4m3 rows), and so does the weight stream."""
+        (_, N13, d), (_, _, F_) = L.w13.shape, L.w2.shape
+        return (ops.moe_mxfp4_a8_ok(2, d, 2, L.w13, swiglu=True) and ops.moe_mxfp4_a8_ok(2, F_, 2, L.w2)
+                and ops.moe_skinny_mxfp4_ok(2, d, 2, L.w13, swiglu=True) and ops.moe_skinny_mxfp4_ok(2, F_, 2, L.w2))
 
     def tune_gemms(self, M: int, bucket: bool = False, lm_head: bool = True, only=None) -> None:
         """The bf16 vocabulary projection is the MoE decoder's one dense bf16 GEMM (attention projections and
@@ -256,6 +273,18 @@ class MixtralModel(TensorParallel, LlamaModel):
             aq, as_ = ops.quant_fp8_rows(act)
             return ops.grouped_gemm(aq, L.w2, row_off, a_scale=as_, w_scale=L.s2)
         if isinstance(L.w13, ops.Mxfp4Experts):
+            if self.expert_act == "e4m3":
+                n = rows if rows is not None else (a_rows.numel() if a_rows is not None else x.shape[0])
+                ok = (x.dim() == 2 and ops.moe_mxfp4_a8_ok(x.shape[0], x.shape[1], n, L.w13, swiglu=True)
+                      and ops.moe_mxfp4_a8_ok(n, L.w2.shape[2], n, L.w2))
+                if ops.moe_mxfp4_a8_route(n, L.w13.shape[0], ok) == "a8":
+                    # the T token rows quantised once (the kernel gathers the T * k routed rows), then the SwiGLU
+                    # output per row
+                    act = ops.moe_swiglu_mxfp4_a8(x, L.w13, row_off, a_rows, rows)
+                    return ops.moe_linear_mxfp4_a8(act, L.w2, row_off)
+                if self.moe_scratch is None and n > ops.MOE_MXFP4_STREAM_AVG_ROWS * L.w13.shape[0]:
+                    raise RuntimeError("MXFP4 experts: the W4A8 kernel does not take this step's rows and the model "
+                                       "holds no dequantisation scratch")
             act = ops.moe_swiglu_mxfp4(x, L.w13, row_off, a_rows, rows, self.moe_scratch)
             return ops.moe_linear_mxfp4(act, L.w2, row_off, self.moe_scratch)
         gu = ops.grouped_gemm(x, L.w13, row_off, a_rows=a_rows, rows=rows)

@@ -10,7 +10,8 @@ what the routing kernels compute.  With 128 experts ``ops.route`` takes the wide
 One device only: tensor and expert parallelism are refused at construction, and so is the use as an embedder
 (``config.check_variant``).  ``fp8=True`` quantises the experts at load (gate|up interleaved in blocks of 32) and
 holds the attention projections as ``ops.Fp8Weight``, as for Mixtral.  ``expert_weights="mxfp4"`` holds the experts
-as ``ops.Mxfp4Experts`` (weight-only, everything else bf16), as for Mixtral too.
+as ``ops.Mxfp4Experts`` (weight-only, everything else bf16), as for Mixtral too, and ``expert_act="e4m3"`` runs their
+large steps with e4m3 activations (``ops.moe_gemm_mxfp4_a8``).
 """
 from __future__ import annotations
 
@@ -28,13 +29,15 @@ class Qwen3MoeModel(MixtralModel):
 
     def __init__(self, cfg: DecoderConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  weights_path: Optional[str] = None, max_position: Optional[int] = None, fp8: bool = False,
-                 tp_size: int = 1, ep_size: int = 1, mxfp4: bool = False, expert_weights: str = "bf16"):
+                 tp_size: int = 1, ep_size: int = 1, mxfp4: bool = False, expert_weights: str = "bf16",
+                 expert_act: str = "bf16"):
         if not (cfg.num_experts and cfg.qk_norm):
             raise ValueError(f"{cfg.name} is not a Qwen3-MoE decoder (a MoE config with qk_norm)")
         if tp_size > 1 or ep_size > 1:
             raise ValueError(f"{cfg.name}: Qwen3-MoE decoders run on one device (tp_size {tp_size}, ep_size {ep_size})")
         super().__init__(cfg, device=device, dtype=dtype, seed=seed, weights_path=weights_path,
-                         max_position=max_position, fp8=fp8, mxfp4=mxfp4, expert_weights=expert_weights)
+                         max_position=max_position, fp8=fp8, mxfp4=mxfp4, expert_weights=expert_weights,
+                         expert_act=expert_act)
 
     def _random_init(self, seed: int) -> None:
         """Mixtral's tensors from Mixtral's generator, then the q / k norm weights of every layer from a generator

@@ -672,6 +672,75 @@ def swiglu_mxfp4_a8(x, w: Mxfp4Weight, block: int) -> torch.Tensor:
     return silu_mul(gemm_mxfp4_a8(xq, xs, w), block=block)
 
 
+# MoE experts in MXFP4 with e4m3 activations (csrc/kernels/moe_mxfp4_a8.hip): the grouped form of gemm_mxfp4_a8.  A
+# model built with ``expert_act="e4m3"`` takes it where the weight stream ends (``rows > MOE_MXFP4_STREAM_AVG_ROWS
+# * E``): no dequantised stack, no scratch.
+
+def moe_mxfp4_a8_ok(a_nrows: int, lda: int, rows: int, w: Mxfp4Experts, swiglu: bool = False) -> bool:
+    """Whether :func:`moe_gemm_mxfp4_a8` takes the shape: the kernel's divisibility rules (``lda`` in bytes of the
+    e4m3 rows) and a grid of at most 2^31 - 1 workgroups."""
+    try:
+        E, N, K = (int(v) for v in w.shape)
+        a_nrows, lda, rows = int(a_nrows), int(lda), int(rows)
+    except (AttributeError, TypeError, ValueError):
+        return False
+    if E < 1 or K <= 0 or K % 128 or N % (64 if swiglu else 16) or a_nrows < 0 or not 0 <= rows < (1 << 31):
+        return False
+    if a_nrows > 1 and (lda % 16 or lda < K):
+        return False
+    return ((rows + 127) // 128 + E) * (((N + 127) // 128 + 7) // 8) * 8 < (1 << 31)
+
+
+def moe_gemm_mxfp4_a8(xq: torch.Tensor, xs: torch.Tensor, w: Mxfp4Experts, row_off: torch.Tensor,
+                      a_rows: Optional[torch.Tensor] = None, rows: Optional[int] = None,
+                      out: Optional[torch.Tensor] = None, swiglu: bool = False) -> torch.Tensor:
+    """Grouped :func:`gemm_mxfp4_a8` over an expert stack, one launch: rows ``[row_off[e], row_off[e + 1])`` of the
+    result are ``gemm_mxfp4_a8(xq[src], xs[src], W[e])`` of those rows, bit for bit (``swiglu``: over a 32-row
+    gate/up interleaved W[e], output ``[rows, N / 2]``).  ``a_rows`` ``[rows]`` int32 gathers the e4m3 row AND its
+    scale for each output row (the router's ``src_row``: ``xq`` / ``xs`` are the tokens', quantised once); without it
+    ``xq`` holds the expert-major rows.  ``row_off`` ``[E + 1]`` int32 stays on the device: no host step,
+    graph-capturable, correct for any segment lengths.  The stack is read as stored: no scratch."""
+    if rows is None:
+        rows = a_rows.numel() if a_rows is not None else xq.shape[0]
+    if out is None:
+        out = torch.empty(rows, w.shape[1] // 2 if swiglu else w.shape[1], dtype=torch.bfloat16, device=xq.device)
+    kernels().moe_gemm_mxfp4_a8(xq, xs.reshape(-1), w.q, w.s, out, row_off, a_rows, 2 if swiglu else 0)
+    return out
+
+
+def _a8_pair(x):
+    if isinstance(x, QAct):
+        return x.q, x.s
+    return x if isinstance(x, tuple) else quant_fp8_rows(x)
+
+
+def moe_swiglu_mxfp4_a8(x, w13: Mxfp4Experts, row_off: torch.Tensor, a_rows: Optional[torch.Tensor],
+                        rows: Optional[int]) -> torch.Tensor:
+    """The experts' gate|up projection with its SwiGLU over an MXFP4 stack (rows gate / up interleaved in blocks of
+    32 per expert) with e4m3 activations -> ``[rows, F]`` bf16, expert-major.  ``x``: the T token rows in bf16
+    (quantised per row here, once: the kernel gathers the T * k routed rows through ``a_rows``), a :class:`QAct`, or
+    an ``(xq, xs)`` pair."""
+    xq, xs = _a8_pair(x)
+    return moe_gemm_mxfp4_a8(xq, xs, w13, row_off, a_rows=a_rows, rows=rows, swiglu=True)
+
+
+def moe_linear_mxfp4_a8(act, w2: Mxfp4Experts, row_off: torch.Tensor) -> torch.Tensor:
+    """The experts' down projection of expert-major rows over an MXFP4 stack with e4m3 activations ->
+    ``[rows, d]`` bf16; ``act`` as ``x`` of :func:`moe_swiglu_mxfp4_a8`."""
+    aq, as_ = _a8_pair(act)
+    return moe_gemm_mxfp4_a8(aq, as_, w2, row_off)
+
+
+def moe_mxfp4_a8_route(rows: int, E: int, ok: bool) -> str:
+    """Where an ``expert_act="e4m3"`` step's expert FFN runs, from the routed rows, the expert count and
+    :func:`moe_mxfp4_a8_ok` alone (never a timing): "stream" (the weight stream, bf16 activations) up to
+    ``MOE_MXFP4_STREAM_AVG_ROWS`` rows per expert on average, then "a8", or "dequant" for a shape the W4A8 kernel
+    does not take."""
+    if rows <= MOE_MXFP4_STREAM_AVG_ROWS * E:
+        return "stream"
+    return "a8" if ok else "dequant"
+
+
 def gemm4w(A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, swiglu: bool = False, bias: Optional[torch.Tensor] = None,
            gelu: bool = False, bn: int = 256, chain: "Optional[NormChain]" = None, var: int = 0,

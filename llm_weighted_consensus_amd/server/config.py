@@ -33,6 +33,13 @@ variables configure the local engine:
                     csrc/kernels/moe_mxfp4.hip, large ones dequantise into a scratch and run the bf16 grouped
                     GEMM.  Refused for any other value, on dense archs, with "fp8", "tp" > 1, "adapters" and
                     in LWC_EMBED_MODELS; "mxfp4": true stays refused on MoE archs
+                    "expert_act": "e4m3" (with "expert_weights": "mxfp4"; default "bf16") runs the expert FFN
+                    of every step past 32 routed rows per expert on average — prefill, mixed steps, large
+                    decode batches — with per-row e4m3 activations on the block-scaled MFMA, reading the
+                    packed expert stacks directly (csrc/kernels/moe_mxfp4_a8.hip): no dequantisation pass,
+                    and the model allocates no dequantisation scratch; smaller steps stay the
+                    bf16-activation weight stream.  Refused without "expert_weights": "mxfp4" and for any
+                    other value
   LWC_EMBED_MODELS  JSON {name: {"arch": "bge-large-en-v1.5", "weights": "random:<seed>" | <path>}}
   LWC_GPU           device index for this process's engine (one process per GPU)
   LWC_GPUS          comma list of devices: serve each model through an EngineGroup (one worker process

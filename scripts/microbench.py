@@ -1438,6 +1438,127 @@ def moe_mxfp4_ab(dev):
     print("wrote", out)
 
 
+def moe_mxfp4_a8_ab(dev):
+    """MoE experts in MXFP4 with e4m3 activations (profiles/moe_mxfp4_a8.md).  (a) the expert FFN of one layer at the
+    eight shapes of the README's MXFP4-experts table: W4A8 (``quant_fp8_rows`` of the T token rows, the gathered
+    gate|up + SwiGLU, ``quant_fp8_rows`` of its output, down: both quantisation passes inside the timing), the parent's
+    path at that row count (the weight stream up to ``MOE_MXFP4_STREAM_AVG_ROWS`` rows per expert, the dequantise
+    path above), bf16 experts and fp8 experts; (b) one qwen3-30b-a3b decode step at 4 layers with bf16 experts, with
+    MXFP4 experts and with ``expert_act="e4m3"`` on top; (c) GiB allocated after the load.  Arms interleaved in one
+    process, medians of 7 rounds of captured graphs; the MXFP4 stacks rotate over 3 copies where one would fit the
+    last-level cache."""
+    from pathlib import Path
+    from types import SimpleNamespace
+
+    from llm_weighted_consensus_amd import ops
+    from llm_weighted_consensus_amd.models.config import decoder_config
+    from llm_weighted_consensus_amd.models.mixtral import MixtralModel, MoELayerWeights
+    from llm_weighted_consensus_amd.models.qwen_moe import Qwen3MoeModel
+
+    out = Path(os.environ.get("MOEMXFP4A8_OUT",
+                              Path(__file__).resolve().parent.parent / "profiles" / "moe_mxfp4_a8.md"))
+    shapes = {"qwen3-30b-a3b": (1, 64, 512, 4096), "mixtral-8x7b": (16, 128, 256, 512)}
+    lines = ["# MoE experts in MXFP4 with e4m3 activations: the grouped W4A8 kernel "
+             "(`python scripts/microbench.py moemxfp4a8`)", "",
+             f"MI355X, torch {torch.__version__}.  Arms interleaved in one process, median of 7 rounds; every arm is a "
+             "captured graph of several calls.", "",
+             "## (a) Expert FFN of one layer: gate|up + SwiGLU + down", "",
+             "Rows are the (token, slot) pairs `ops.route` makes of T N(0, 1) tokens and a random router.  W4A8: "
+             "`quant_fp8_rows` of the T token rows, `moe_gemm_mxfp4_a8` with the gather and the SwiGLU epilogue, "
+             "`quant_fp8_rows` of its output, `moe_gemm_mxfp4_a8` (both quantisation passes are timed).  parent: what "
+             "a model without `expert_act` runs at that row count, the weight stream (`moe_skinny_mxfp4` twice) up to "
+             f"{ops.MOE_MXFP4_STREAM_AVG_ROWS} rows per expert on average, above it the dequantise path "
+             "(`mxfp4_dequant` of each stack, then the bf16 arm).  bf16: `grouped_gemm`, `silu_mul`, `grouped_gemm`; "
+             "fp8: the model's fp8 branch on rows quantised outside the timing.  routed: whether a model with "
+             "`\"expert_act\": \"e4m3\"` takes the W4A8 kernel at that row count.", "",
+             "| shapes | T | rows / expert | active | routed | W4A8 us | parent us (path) | bf16 us | fp8 us | "
+             "W4A8 / parent | W4A8 / bf16 | W4A8 / fp8 |", "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*shape, std=0.02):
+        return (torch.randn(*shape, device=dev, generator=g) * std).to(torch.bfloat16)
+
+    def rand_stack(E, N, K):  # timing only: any codes, scales near 2^-6
+        st = ops.Mxfp4Experts.__new__(ops.Mxfp4Experts)
+        st.q = torch.randint(0, 256, (E, N, K // 2), device=dev, dtype=torch.uint8)
+        st.s = torch.randint(117, 125, (E, N, K // 32), device=dev, dtype=torch.uint8)
+        st.shape = (E, N, K)
+        return st
+
+    def mark(r):
+        return f"**{r:.2f} (slower)**" if r > 1 else f"{r:.2f}"
+
+    for arch, Ts in shapes.items():
+        cfg = decoder_config(arch)
+        d, F_, E, k = cfg.hidden, cfg.ffn, cfg.num_experts, cfg.experts_per_token
+        w13 = torch.stack([ops.swiglu_interleave(rnd(2 * F_, d)) for _ in range(E)])
+        w2 = rnd(E, d, F_)
+        q13, s13 = ops.quant_fp8_weight(w13)
+        q2, s2 = ops.quant_fp8_weight(w2)
+        copies = 3 if E * 3 * F_ * d * 17 // 32 < (512 << 20) else 1
+        mx = _rotating([(rand_stack(E, 2 * F_, d), rand_stack(E, d, F_)) for _ in range(copies)])
+        scratch = torch.empty(E * 2 * F_ * d, dtype=torch.bfloat16, device=dev)
+        router = rnd(E, d, std=0.1)
+        me = SimpleNamespace(fp8=True, moe_scratch=scratch)
+        L8 = MoELayerWeights(None, None, None, None, router, q13, q2, s13, s2, 32)
+        for T in Ts:
+            h = torch.randn(T, d, device=dev, generator=g).to(torch.bfloat16)
+            _, _, row_off, src, _ = ops.route(h, router, k)
+            rows = T * k
+            active = int((row_off.diff() > 0).sum())
+            hq, hs = ops.quant_fp8_rows(h)
+            path = "stream" if rows <= ops.MOE_MXFP4_STREAM_AVG_ROWS * E else "dequant"
+
+            def bf16():
+                gu = ops.grouped_gemm(h, w13, row_off, a_rows=src, rows=rows)
+                return ops.grouped_gemm(ops.silu_mul(gu, block=32), w2, row_off)
+
+            def parent():
+                a, b = mx()
+                act = ops.moe_swiglu_mxfp4(h, a, row_off, src, rows, scratch, path=path)
+                return ops.moe_linear_mxfp4(act, b, row_off, scratch, path=path)
+
+            def a8():
+                a, b = mx()
+                act = ops.moe_swiglu_mxfp4_a8(h, a, row_off, src, rows)
+                return ops.moe_linear_mxfp4_a8(act, b, row_off)
+
+            t = _graph_medians({"a8": a8, "parent": parent, "bf16": bf16,
+                                "fp8": lambda: MixtralModel._experts(me, hq, row_off, L8, hs, a_rows=src, rows=rows)},
+                               10 if rows <= 1024 else 3)
+            routed = "yes" if ops.moe_mxfp4_a8_route(rows, E, True) == "a8" else "no"
+            lines.append(f"| {arch} | {T} | {rows / E:.2f} | {active} / {E} | {routed} | {t['a8']:.1f} | "
+                         f"{t['parent']:.1f} ({path}) | {t['bf16']:.1f} | {t['fp8']:.1f} | "
+                         + " | ".join(mark(t["a8"] / t[a]) for a in ("parent", "bf16", "fp8")) + " |")
+            print(lines[-1], flush=True)
+        del w13, w2, q13, q2, s13, s2, mx, scratch, L8, me
+        torch.cuda.empty_cache()
+
+    lines += ["", "## (b) One decode step, qwen3-30b-a3b shapes at 4 layers (context 32, captured graph)", "",
+              "| experts | B | step ms | vs bf16 | vs mxfp4 |", "|---|---|---|---|---|"]
+    cfg = decoder_config("qwen3-30b-a3b", layers=4)
+    gib, steps = {}, {}
+    for name, kw in (("bf16", {}), ("mxfp4", {"expert_weights": "mxfp4"}),
+                     ("mxfp4 + e4m3", {"expert_weights": "mxfp4", "expert_act": "e4m3"})):
+        torch.cuda.empty_cache()
+        before = torch.cuda.memory_allocated(dev)
+        model = Qwen3MoeModel(cfg, device=dev, seed=0, max_position=128, **kw)
+        torch.cuda.synchronize()
+        gib[name] = (torch.cuda.memory_allocated(dev) - before) / 2 ** 30
+        for B in (64, 512, 4096):
+            steps[name, B] = step = _decode_step_ms(model, cfg, dev, B)[0]
+            lines.append(f"| {name} | {B} | {step:.3f} | {mark(step / steps['bf16', B])} | "
+                         + (mark(step / steps["mxfp4", B]) if ("mxfp4", B) in steps else "") + " |")
+            print(lines[-1], flush=True)
+        del model
+    lines += ["", "## (c) GiB allocated after the load (qwen3-30b-a3b shapes at 4 layers; the dequantisation scratch, "
+              "0.75 GiB, is what `expert_act` drops)", "",
+              "| experts | GiB |", "|---|---|"] + [f"| {f} | {v:.2f} |" for f, v in gib.items()]
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["gemm", "attn", "sample", "small"])
@@ -1475,6 +1596,8 @@ def main():
         qwen_moe(dev)
     if "moemxfp4" in a.what:
         moe_mxfp4_ab(dev)
+    if "moemxfp4a8" in a.what:
+        moe_mxfp4_a8_ab(dev)
     if "g48" in a.what:
         g48_ab(dev)
     if "g8ab" in a.what:
